@@ -22,7 +22,14 @@ and N=8 8x8 = 64 tiles sharded 8-way, 8 per GPU (BASELINE.json configs[3]).  The
 the ranks (explicit opt-in shard_patches=True; coarse branch + G2L replicated, no communication) and the per-tile
 depths are all-gathered over RCCL before every rank stitches.  value = tiles of the image / max-over-ranks wall time.
 
-Rank 0 prints ONE JSON line (contract in the task statement) including
+A plain run sets up, warms up, times the K steps of the headline mode, writes the outputs of its last timed step if
+--dump-outputs DIR is given, and rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, config,
+memory; rank_seconds at N > 1).  --dump-outputs DIR (e.g. bench_outputs) writes the stitched depth map the timed path returned in
+its last step as DIR/depth.npy (float32, [1, 1, 1568, 2072] = 13 MB at the default geometry); the image and the weights are seeded, so the
+same arguments give the same inputs in every run.
+
+--full adds the measurements that take runs of their own (each still switchable off with its --no-* option):
+  rccl         : (N > 1) the communicator's size after a real collective and the tile-depth gather of one pass on its own
   roofline     : the dominant launch of the headline mode (of the 3x3 conv 544->544 @ 8x392x518, the largest single layer of the
                  fusion U-Net: in the default dispatch the batched split-precision GEMM over its 36 Winograd transform points) timed
                  live with HIP events on its launch stream: USEFUL float32 FLOPs vs the f32 MFMA peak (+ executed bf16 FLOPs vs the bf16 peak)
@@ -65,6 +72,10 @@ def main():
     ap.add_argument("--encoder", default="vitl")
     ap.add_argument("--process-num", type=int, default=8)
     ap.add_argument("--split", default=None, help="override the tile grid, e.g. 8x16 (kernel / scaling experiments)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements: roofline launches, the f32-MFMA-only and bf16 passes, the CPU baseline, the RCCL gather")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary bf16 leg")
@@ -154,6 +165,8 @@ def main():
         return dt, d
 
     dt, depth = run_mode(args.dtype)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, depth=depth)
     ms = dt / args.steps * 1e3
     value = P * args.steps / dt
     per_gpu = P // N
@@ -179,16 +192,17 @@ def main():
                          "PF_WS_CAP_GB = 2.5 GB: larger layers run as sub-batches of their tiles); PatchFusion.free_parameters() (opt-in) returns another ~2.7 GB")
     if world > 1:
         out["rank_seconds"] = rank_s[args.dtype]
+    if world > 1 and args.full:
         # self-diagnosis of the first real multi-GPU run (round-5 review item 8): the communicator's own size after an actual collective on the device, and
         # the tile-depth gather of one image pass on its own -- [P, 392, 518] float32 through patchfusion_amd.dist.all_gather_shards (one
         # all_gather_into_tensor over RCCL), timed with a barrier on both sides, maximum over ranks, after one untimed call (RCCL sets its rings up lazily)
         out["rccl"] = gather_diagnosis(P, (392, 518), world, dev, barrier, ms)
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         out["roofline"] = roofline(args.dtype, dev)
         if args.dtype == "fp32" and split3_on():
             out["roofline"]["attention"] = roofline_attention(dev)       # the second north-star kernel beside the dominant launch (round-5 review item 7)
         log(f"roofline: {out['roofline']}")
-    if N == 1 and args.dtype == "fp32" and not args.no_secondary and split3_on():
+    if N == 1 and args.dtype == "fp32" and args.full and not args.no_secondary and split3_on():
         # the same pass with every GEMM on the float32 MFMA (PF_LINEAR_SPLIT3=0 PF_WINO_SPLIT3=0): the number to quote if split-precision linears are not
         # accepted as "float32", and the measured distance between the two float32 evaluations
         os.environ["PF_LINEAR_SPLIT3"] = "0"
@@ -204,7 +218,7 @@ def main():
                                 "max_abs_depth_diff_vs_headline": float(d3.max()), "mean_abs_depth_diff_vs_headline": float(d3.mean())}
         log(f"f32 MFMA only: {out['f32_mfma_only']}")
         del depth3
-    if N == 1 and args.dtype == "fp32" and not args.no_secondary:
+    if N == 1 and args.dtype == "fp32" and args.full and not args.no_secondary:
         dt2, depth2 = run_mode("bf16")
         diff = (depth2 - depth).abs().flatten()
         sec = {"value": round(P * args.steps / dt2, 3), "unit": "patches/s", "ms_per_step": round(dt2 / args.steps * 1e3, 3),
@@ -216,13 +230,22 @@ def main():
             sec["roofline"] = roofline("bf16", dev)
         out["bf16"] = sec
         log(f"bf16 secondary: {sec}")
-    if rank == 0 and N == 1 and not args.no_cpu_baseline:
+    if rank == 0 and N == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, sd, img.cpu())
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         barrier()                      # the other ranks wait for rank 0's roofline launch, then all leave together
         torch.distributed.destroy_process_group()
+
+
+def dump_outputs(dirname, **arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (what the timed path returned in its last step)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), t.detach().float().cpu().numpy())
+    log(f"outputs of the last timed step written to {dirname}: {', '.join(sorted(arrays))}")
 
 
 def gather_diagnosis(P, tile_hw, world, dev, barrier, ms_per_step):
@@ -300,7 +323,9 @@ def dry_run(args):
         cs = [torch.zeros_like(c) for _ in range(world)]
         dist.all_gather(cs, c)
         assert all(float(v) == float(cs[0]) for v in cs), "ranks disagree on the stitched map"
-    comm = gather_diagnosis(P, ps, world, torch.device("cpu"), barrier, dt / args.steps * 1e3) if world > 1 else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, depth=d)
+    comm = gather_diagnosis(P, ps, world, torch.device("cpu"), barrier, dt / args.steps * 1e3) if world > 1 and args.full else None
     if rank == 0:
         print(json.dumps({
             "metric": "patches/sec (DRY RUN of the multi-rank protocol on CPU tensors -- not a measurement)", "value": round(P * args.steps / dt, 3),
@@ -552,14 +577,14 @@ def roofline(dtype, dev, gemm_only=False):
 
 
 def cpu_baseline(cfg, sd, img):
-    """CPU path on this box's host cores, bounded sample (threads capped at 64: with all 256 hardware threads of the GPU box
-    torch's CPU kernels oversubscribe -- measured 108 s instead of ~5 s for one branch forward).
+    """CPU path on this box's host cores, bounded sample (threads = OMP_NUM_THREADS when set, capped at 64: with all 256 hardware threads of
+    the GPU box torch's CPU kernels oversubscribe -- measured 108 s instead of ~5 s for one branch forward).
     kind 'reference': the reference's own `PatchFusion` (imported through oracle/ref_shim.py) on a 1x1-tile 4K image = ONE
         patch through coarse branch + fine branch + fusion (the G2L stacks inside the fusion call, reference schedule);
         only possible where /root/reference exists (not on the GPU box).
     kind 'port': the oracle restatement, ONE tile of the same workload = fine branch + fusion_forward (4029.9 GFLOP, G2L
         hoisted like the engine does); the coarse pass + G2L it needs are computed untimed."""
-    cores = min(os.cpu_count() or 1, 64)
+    cores = min(int(os.environ.get("OMP_NUM_THREADS") or 0) or os.cpu_count() or 1, 64)
     torch.set_num_threads(cores)
     from oracle import ref_shim
     if ref_shim.reference_available():

@@ -1,12 +1,17 @@
 """`PatchFusion.forward(mode='train')` (patchfusion.py:372-399) -- FORWARD VALUE of the training step
 (coarse branch on a batch of images, fine branch on one crop per image, coarse_postprocess_train, fusion_forward, SILogLoss).
-  * the oracle restatement (pf_oracle.Oracle.train_forward) against the reference's own Python (build container only),
+  * the oracle restatement (pf_oracle.Oracle.train_forward) against the reference's own outputs (tests/golden/reference_live.npz,
+    made by oracle/make_golden.py live),
   * the engine wiring (torch stand-in ops) against the oracle.
 The HIP kernels of the same path are checked in tests/test_e2e_gpu.py::test_train_mode_forward_vs_oracle."""
+import os
+
+import numpy as np
 import pytest
 import torch
 
 from oracle import pf_oracle
+from oracle.make_golden import stored_diff
 from patchfusion_amd.config import make_config
 from patchfusion_amd.model import PatchFusion
 from patchfusion_amd.spec import patchfusion_spec, synthetic_state_dict
@@ -56,19 +61,11 @@ def test_silog_degenerate_mask_returns_zero(tiny):
     assert float(pf_oracle.silog_loss(pred, gt, 1e-3, 80).abs().max()) == 0.0
 
 
-@pytest.mark.reference
-def test_oracle_train_forward_matches_reference_live(tiny):
-    from oracle import ref_shim
-    if not ref_shim.reference_available():
-        pytest.skip("reference tree not present")
+def test_oracle_train_forward_matches_reference_live(tiny, golden_dir):
+    g = np.load(os.path.join(golden_dir, "reference_live.npz"))
+    ref_loss = float(g["train_total_loss"])
     cfg, sd = tiny
-    PF = ref_shim.import_reference()
-    with ref_shim.in_reference_cwd():
-        ref = PF(cfg).eval()
-    ref.load_state_dict(sd, strict=True)
     image_lr, crops, bboxs, gt = train_batch()
-    with torch.no_grad():
-        loss_dict, aux = ref(mode="train", image_lr=image_lr, image_hr=None, crops_image_hr=crops, crop_depths=gt, bboxs=bboxs)
     o_loss, o_pred = pf_oracle.Oracle(cfg, sd).train_forward(image_lr, crops, gt, bboxs)
-    assert float((aux["depth_pred"] - o_pred).abs().max()) < 1e-5
-    assert abs(float(loss_dict["total_loss"]) - float(o_loss)) < 1e-5 * max(1.0, abs(float(o_loss)))
+    assert stored_diff(g, "train_depth_pred", o_pred) < 1e-5
+    assert abs(ref_loss - float(o_loss)) < 1e-5 * max(1.0, abs(float(o_loss)))

@@ -5,9 +5,9 @@
 #   the attention roofline in a fresh process.
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 mkdir -p gpurun_out; export TMPDIR=/tmp; O=gpurun_out; TAG=${1:-r6}
-( timeout 900 python bench.py --steps 20 --warmup 5 ) > $O/${TAG}_bench_default.log 2> $O/${TAG}_bench_default.err
+( timeout 900 python bench.py --steps 20 --warmup 5 --full ) > $O/${TAG}_bench_default.log 2> $O/${TAG}_bench_default.err
 ( timeout 600 python bench.py --split 2x4 --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-secondary ) > $O/${TAG}_shard_times.log 2>&1
-( timeout 600 python bench.py --encoder vits --process-num 4 --steps 10 --warmup 3 --no-cpu-baseline --no-roofline ) > $O/${TAG}_bench_vits.log 2>&1
+( timeout 600 python bench.py --encoder vits --process-num 4 --steps 10 --warmup 3 --full --no-cpu-baseline --no-roofline ) > $O/${TAG}_bench_vits.log 2>&1
 ( timeout 300 python -c "
 import json, torch, bench
 print(json.dumps(bench.roofline_attention(torch.device('cuda', 0))))" ) > $O/${TAG}_attention_fresh_process.log 2>&1
