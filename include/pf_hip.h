@@ -83,6 +83,19 @@ int pf_conv_winograd_split3(const pf_conv_params* p, const void* U3, int u_rows,
  * identical results for every window.  With more than one window the output of window k is written before the input of window k + 1 (and its one-pixel
  * halo) is read: x and y must NOT overlap then (PF_ERR_ARG); a residual may alias y (it is read at the pixels being written). */
 int pf_conv_winograd_split3_windowed(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, void* V3, void* M, long window, void* stream);
+/* fp16x2 form of the same windowed layer (csrc/wino_f16x2.hip): every operand of the transform-domain GEMM is two fp16 planes with a power-of-two
+ * scale, three f16 MFMAs per product instead of six bf16 ones.  U = PackedConv.wino_u, float32 [36][u_rows][Cin] (u_kpad == Cin, u_rows % 16 == 0);
+ * V2 = arena of 2 x 36 x window x Cin fp16 (window % 8 == 0, 0 = all tiles), M = 36 x window x Cout float32, scratch = pf_wino_f16x2_scratch_bytes
+ * bytes (per-call channel maxima of x, the scaled filter planes and their column exponents).  Same argument rules as the bf16x3 entry, the x / y alias
+ * refusal included.  pf_conv_winograd_f16x2_supported returns 1 when a call qualifies and its product runs on the 192 x 192 kernel (the only tile
+ * with an fp16x2 form), else 0 -- the caller then takes pf_conv_winograd_split3_windowed. */
+long pf_wino_f16x2_scratch_bytes(int cin, int u_rows);
+int pf_conv_winograd_f16x2_supported(const pf_conv_params* p, int u_rows, int u_kpad, long window);
+int pf_conv_winograd_f16x2_windowed(const pf_conv_params* p, const void* U, int u_rows, int u_kpad, void* V2, void* M, void* scratch, long window,
+                                    void* stream);
+/* its batched product alone: x / w = two fp16 planes each, chunk-major (korder = 6, batch = transform points, no epilogue), y float32 =
+ * ldexp(sum, col_exp[z][n]) with col_exp int32 [batch][w_rows] */
+int pf_gemm_f16x2_points(const pf_conv_params* p, const int* col_exp, int grid_cap, void* stream);
 
 /* FUSED Winograd F(4x4, 3x3) (csrc/wino_fused.hip): the same layers in ONE kernel -- the transformed input and the transform-domain
  * products never exist in HBM.  `p` as for pf_conv_winograd (p->w is not read); `up` = the filters in MFMA fragment order

@@ -623,14 +623,26 @@ __global__ __launch_bounds__(512) void gemm_split3_persist_kernel(const pf_conv_
 // allowed to multiply -- a DMA piece stalls that wave ~100 cycles.  The slot (g+1) & 1 is free from phase 2g on (chunk g-1: read by A in 2g-2, by B
 // in 2g-1), group A reads chunk g+1 in phase 2g+2, so B's pieces have the rest of phase 2g+1 to land: they are the W planes (filters / weights,
 // L2-resident: 250-400 cycles), B waits vmcnt(0) at the end of that phase exactly as before.  Compute phases of both groups are then MFMA-only.
-template <bool BARE, bool BL>
+// F16 (round 7, the fp16x2 Winograd GEMM of csrc/wino_f16x2.hip): TWO fp16 planes per operand, x = 2^e (h + l), and three products per
+// accumulator (w_h.x_l, w_l.x_h, w_h.x_h, smallest first) on v_mfma_f32_16x16x32_f16 -- same cycles per instruction as the bf16 form.  A stage is
+// 2 x 384 rows x 64 B = 48 KiB (6 pieces per wave), a chunk 54 MFMAs per wave (~860 cycles) against 6 pieces + 18 fragment reads.  Only the BARE
+// batched form exists: p.scale then carries int32 column exponents [batch][w_rows], and the epilogue stores ldexp(acc, f[z][n]) (exact: powers of two).
+// NSL = ring slots.  With half the MFMAs per chunk the phases are half as long, and a piece issued one chunk ahead (two phases) no longer lands in
+// time: the fp16x2 form runs a THREE-slot ring (3 x 48 KiB) and issues chunk g+2 where the two-slot form issues g+1 -- the slot (g+2) % 3 held chunk
+// g-1 (read by A in phase 2g-2, by B in 2g-1), and every wave waits for its pieces of chunk g+1 at the end of phase 2g+1 with vmcnt(PPW): the PPW
+// newest vector-memory operations of the wave are then its pieces of chunk g+2, issued after those of g+1.  Only DMA pieces are counted against DMA
+// pieces -- the epilogue's register loads and stores of the wave sit OLDER than chunk g+2's pieces, so however they retire relative to the pieces
+// they cannot make the count pass early (the DESIGN 4i rule: never count register loads in a hand-counted wait).
+template <bool BARE, bool BL, bool F16 = false, int NSL = 2>
 __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_conv_params p, int mt, int nt, int gm, int total, int flags) {
-  constexpr int BM = 192, BN = 192, WM = 4, WN = 2, NP = 3, NS = 2;
+  static_assert(!F16 || BARE, "fp16x2: batched transform-domain GEMM only");
+  static_assert(NSL == 2 || (NSL == 3 && BL), "three ring slots: the BL schedule only");
+  constexpr int BM = 192, BN = 192, WM = 4, WN = 2, NP = F16 ? 2 : 3, NS = NSL, NTERM = F16 ? 3 : 6, LEAD = NS - 1;
   constexpr int NW = WM * WN;
   constexpr int WTM = BM / WM, WTN = BN / WN, FM = WTM / 16, FN = WTN / 16;
   constexpr int ROWS = NP * (BM + BN), PIECES = ROWS / 16, PPW = PIECES / NW;
   constexpr int STAGE = ROWS * 64;
-  constexpr int NMF = 6 * FN * FM, MPP = NMF / PPW;            // MFMAs per chunk and wave; MFMAs between two pieces of group B
+  constexpr int NMF = NTERM * FN * FM, MPP = NMF / PPW;        // MFMAs per chunk and wave; MFMAs between two pieces of group B
   static_assert(PPW * 16 * WM == NP * BM && WM * 2 == NW && BM == BN && NMF % PPW == 0, "waves 0..3 stage the X planes, waves 4..7 the W planes");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -702,7 +714,8 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
   unsigned dst_cur = 0;
   setup_loader(l_load);
   auto begin_issue = [&]() __attribute__((always_inline)) {     // cursor of the next chunk to load: ring slot, chunk within the tile, tile switch
-    s_issue ^= 1;
+    if constexpr (NS == 2) s_issue ^= 1;
+    else s_issue = s_issue + 1 == NS ? 0 : s_issue + 1;
     if (++l_kc == nk) {
       l_kc = 0;
       l_load += nb;
@@ -752,7 +765,8 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
   int s_read = 0;
   auto read_frags = [&]() __attribute__((always_inline)) {
     const char* S = smem + s_read * STAGE;
-    s_read ^= 1;
+    if constexpr (NS == 2) s_read ^= 1;
+    else s_read = s_read + 1 == NS ? 0 : s_read + 1;
 #pragma unroll
     for (int pl = 0; pl < NP; ++pl) {
 #pragma unroll
@@ -770,13 +784,22 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
       piece(((TI) * FN * FM + fn * FM + fm) / MPP);                                                                            \
       __builtin_amdgcn_sched_barrier(0);                                                                                       \
     }                                                                                                                          \
-    if (fn < NFN_MIN || fn < cur_nfn)                                                                                          \
-      acc[fn][fm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, f.w[PW][fn]), __builtin_bit_cast(bf16x8, f.x[PX][fm]), \
-                                                            acc[fn][fm], 0, 0, 0);                                             \
+    if (fn < NFN_MIN || fn < cur_nfn) {                                                                                        \
+      if constexpr (F16)                                                                                                       \
+        acc[fn][fm] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, f.w[PW][fn]), __builtin_bit_cast(f16x8, f.x[PX][fm]), \
+                                                             acc[fn][fm], 0, 0, 0);                                            \
+      else                                                                                                                     \
+        acc[fn][fm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, f.w[PW][fn]), __builtin_bit_cast(bf16x8, f.x[PX][fm]), \
+                                                              acc[fn][fm], 0, 0, 0);                                           \
+    }                                                                                                                          \
   }
   auto multiply = [&](auto with_issue) __attribute__((always_inline)) {
     constexpr bool ISS = decltype(with_issue)::value;
-    S3_TERM192(0, 0, 2) S3_TERM192(1, 2, 0) S3_TERM192(2, 1, 1) S3_TERM192(3, 0, 1) S3_TERM192(4, 1, 0) S3_TERM192(5, 0, 0)
+    if constexpr (F16) {
+      S3_TERM192(0, 0, 1) S3_TERM192(1, 1, 0) S3_TERM192(2, 0, 0)
+    } else {
+      S3_TERM192(0, 0, 2) S3_TERM192(1, 2, 0) S3_TERM192(2, 1, 1) S3_TERM192(3, 0, 1) S3_TERM192(4, 1, 0) S3_TERM192(5, 0, 0)
+    }
   };
 #undef S3_TERM192
 
@@ -805,6 +828,10 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
       const int n = e_n0 + wn * e_wtn + fsel * 16 + fg * 4;
       const bool nok = n < p.Cout && fsel < e_nfn;
       float4 bias_r = make_float4(0.f, 0.f, 0.f, 0.f), scale_r = make_float4(1.f, 1.f, 1.f, 1.f);
+      int4 fexp = make_int4(0, 0, 0, 0);
+      if constexpr (F16) {
+        if (nok) fexp = *reinterpret_cast<const int4*>(reinterpret_cast<const int*>(p.scale) + (long)e_z * p.w_rows + n);
+      }
       if constexpr (!BARE) {
         if (nok) {
           if (p.bias) bias_r = *reinterpret_cast<const float4*>(p.bias + n);
@@ -825,6 +852,11 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
           v[1][r] = lo ? recv : b[r];
         }
         const int m1 = e_m0 + wm * WTM + fm * 16 + (fr & 7);
+        if constexpr (F16) {
+          const int fe[4] = {fexp.x, fexp.y, fexp.z, fexp.w};
+#pragma unroll
+          for (int r = 0; r < 4; ++r) { v[0][r] = ldexpf(v[0][r], fe[r]); v[1][r] = ldexpf(v[1][r], fe[r]); }
+        }
         if constexpr (BARE) {
           float* yb = reinterpret_cast<float*>(p.y) + y_base;
           if (nok && m1 < M) *reinterpret_cast<float4*>(yb + (long)m1 * p.y_ld + n) = make_float4(v[0][0], v[0][1], v[0][2], v[0][3]);
@@ -924,8 +956,17 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
   // timeline against a ~1870-cycle partner phase, is bound by the CU's own store issue (~16 B/clk/CU), not by the chip-wide write bandwidth.)
   // ---- the chunk stream
   issue();                                              // chunk 0
-  vm_wait<0>();
+  if (LEAD == 2 && chunks > 1) {
+    issue();                                            // chunk 1 (three slots)
+    vm_wait<PPW>();                                     // chunk 0 has landed; chunk 1 is waited for at the end of phase 1
+  } else {
+    vm_wait<0>();
+  }
   lds_barrier();
+  auto wait_next = [&](int g) __attribute__((always_inline)) {   // this wave's pieces of chunk g+1 have landed
+    if (LEAD == 2 && g + 2 < chunks) vm_wait<PPW>();    // (chunk g+2's PPW pieces, the newest, may fly)
+    else vm_wait<0>();
+  };
   if (wave < NW / 2) {
     // group A: M_A(g) in phase 2g, C_A(g) in phase 2g+1
 #pragma nounroll
@@ -933,7 +974,7 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
       S3_STAMP192(g, 0)
       tile_cursor();
       S3_STAMP192(g, 1)
-      if (g + 1 < chunks) issue();                      // chunk g+1, phase 2g
+      if (g + LEAD < chunks) issue();                   // chunk g+1 (g+2 with three slots), phase 2g
       S3_STAMP192(g, 2)
       read_frags();
       S3_STAMP192(g, 3)
@@ -945,7 +986,7 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
       __builtin_amdgcn_s_setprio(0);
       S3_STAMP192(g, 5)
       tile_advance();
-      vm_wait<0>();                                     // this wave's pieces of chunk g+1 have landed (phase 2g+1)
+      wait_next(g);                                     // this wave's pieces of chunk g+1 have landed (phase 2g+1)
       S3_STAMP192(g, 6)
       plain_barrier();
       S3_STAMP192(g, 7)
@@ -959,11 +1000,11 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
       S3_STAMP192(g, 0)
       tile_cursor();
       S3_STAMP192(g, 1)
-      if (g + 1 < chunks) issue();                      // W pieces of chunk g+1 -> slot (g+1) & 1, phase 2g+1
+      if (g + LEAD < chunks) issue();                   // W pieces of chunk g+1 -> slot (g+1) & 1 (g+2 -> (g+2) % 3), phase 2g+1
       S3_STAMP192(g, 2)
       read_frags();                                     // chunk g
       S3_STAMP192(g, 3)
-      vm_wait<0>();                                     // they have landed before group A reads them in phase 2g+2
+      wait_next(g);                                     // chunk g+1's have landed before group A reads them in phase 2g+2
       S3_STAMP192(g, 4)
       lds_barrier();
       S3_STAMP192(g, 5)
@@ -1118,6 +1159,34 @@ int launch_persist192(const pf_conv_params& p, hipStream_t st, int grid_cap) {
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
 }
 
+// persistent 192 x 192 launch of the fp16x2 form (two planes per operand: 96 KiB of LDS); the batched BARE product only
+int launch_persist192_f16(const pf_conv_params& p, hipStream_t st, int grid_cap) {
+  constexpr int stage = 2 * (192 + 192) * 64;
+  static std::atomic<unsigned long long> done{0};
+  int dev = 0;
+  hipGetDevice(&dev);
+  const unsigned long long bit = 1ull << (dev & 63);
+  if (!(done.load(std::memory_order_acquire) & bit)) {
+    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3_persist192_kernel<true, true, true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * stage);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3_persist192_kernel<true, true, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * stage);
+    done.fetch_or(bit, std::memory_order_release);
+  }
+  const char* sl = getenv("PF_F16_SLOTS");                               // (A/B: 2 = the two-slot ring of the bf16x3 kernel; read per call)
+  const bool three = !(sl && sl[0] == '2');
+  const long M = (long)p.B * p.OH * p.OW;
+  const int mt = (int)((M + 191) / 192), nt = (p.Cout + 191) / 192;
+  const long total = (long)mt * nt * (p.batch > 1 ? p.batch : 1);
+  const int gm = tile_group(nt);
+  int grid = cu_count();
+  if (grid_cap > 0 && grid_cap < grid) grid = grid_cap;
+  if (grid > total) grid = (int)total;
+  grid &= ~7;
+  if (total > 0x7fffffffL || grid < 8) return PF_ERR_ARG;
+  if (three) hipLaunchKernelGGL((gemm_split3_persist192_kernel<true, true, true, 3>), dim3((unsigned)grid), dim3(512), 3 * stage, st, p, mt, nt, gm, (int)total, 8);
+  else hipLaunchKernelGGL((gemm_split3_persist192_kernel<true, true, true, 2>), dim3((unsigned)grid), dim3(512), 2 * stage, st, p, mt, nt, gm, (int)total, 8);
+  return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
+}
+
 template <int BM, int BN, int WM, int WN, int NS, bool PP = false, int NP = 3, bool PLAIN = false>
 int launch(const pf_conv_params& p, hipStream_t st) {
   constexpr int smem = NS * NP * (BM + BN) * 64;
@@ -1223,6 +1292,22 @@ extern "C" int pf_gemm_split3_ex(const pf_conv_params* p, int grid_cap, void* st
   }
   const char* pp = getenv("PF_S3_PP");                    // (A/B switch; read per call)
   return (pp && pp[0] == '0') ? launch<128, 128, 4, 2, 3, false>(*p, st) : launch<128, 128, 4, 2, 3, true>(*p, st);
+}
+
+// fp16x2 batched product of the transform points (csrc/wino_f16x2.hip): x = V planes [2][batch][Cin/32][M][32] fp16 and w = U' planes
+// [2][batch][Cin/32][w_rows][32] fp16 (both chunk-major, korder = 6), y = float32 [batch][M][y_ld] = ldexp(sum_k w.x, col_exp[z][n]).
+extern "C" int pf_gemm_f16x2_points(const pf_conv_params* p, const int* col_exp, int grid_cap, void* stream) {
+  if (!p || !p->x || !p->w || !p->y || !col_exp) return PF_ERR_ARG;
+  const long M = (long)p->B * p->OH * p->OW;
+  if (p->KH != 1 || p->KW != 1 || p->stride != 1 || p->pad != 0 || p->shuffle > 1 || p->korder != 6 || !p->out_f32) return PF_ERR_ARG;
+  if (p->Cin <= 0 || p->Cin % 32 || p->x_ld != p->Cin || p->Kpad != p->Cin || p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || p->w_rows < p->Cout ||
+      p->w_rows % 4)
+    return PF_ERR_ARG;
+  if (M <= 0 || M * 64 >= (1L << 31) || (long)p->w_rows * 64 >= (1L << 31) || p->x_bstride <= 0 || p->w_bstride <= 0) return PF_ERR_ARG;
+  if (p->bias || p->scale || p->res || p->res2 || p->act != PF_ACT_NONE || p->batch > 65535) return PF_ERR_ARG;
+  pf_conv_params q = *p;
+  q.scale = reinterpret_cast<const float*>(col_exp);     // (int32 exponents; the kernel's F16 epilogue reads them as such)
+  return launch_persist192_f16(q, reinterpret_cast<hipStream_t>(stream), grid_cap);
 }
 
 // plain bf16 linear layer through the ping-pong pipeline (see the PLAIN template parameter): x [M][x_ld] bf16, w [w_rows][Kpad] bf16

@@ -15,6 +15,14 @@
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
 
+// csrc/wino_f16x2.hip
+namespace pf_f16x2 {
+int launch_absmax(const float* x, int x_ld, long P, int C, int relu_in, unsigned* cmax, hipStream_t st);
+int launch_u_split(const float* U, int rows, int C, const unsigned* cmax, void* U2, int* fexp, hipStream_t st);
+int launch_input(const float* x, int x_ld, int B, int H, int W, int C, int relu_in, const unsigned* cmax, void* V, int TH, int TW, long tile0, long T,
+                 hipStream_t st);
+}  // namespace pf_f16x2
+
 namespace {
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
@@ -322,7 +330,103 @@ int run_split3(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, 
   return PF_OK;
 }
 
+// fp16x2 form (round 7, csrc/wino_f16x2.hip): per layer call the channel maxima of the input and the scaled filter planes U' (scratch:
+// [2][36][Cin/32][u_rows][32] fp16 | int32 [36][u_rows] column exponents | uint32 [Cin] channel maxima), then per window the input transform into
+// two fp16 planes, the batched 192 x 192 product on three f16 MFMAs per term (pf_gemm_f16x2_points) and the output transform of run_split3.
+// Same windows, same argument rules, one stream.
+struct F16x2Scratch { void* u2; int* fexp; unsigned* cmax; };
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+F16x2Scratch f16x2_scratch(void* base, int cin, int u_rows) {
+  char* b = static_cast<char*>(base);
+  const size_t u2 = align256((size_t)2 * 36 * u_rows * cin * 2), fe = align256((size_t)36 * u_rows * 4);
+  return {b, reinterpret_cast<int*>(b + u2), reinterpret_cast<unsigned*>(b + u2 + fe)};
+}
+
+// the batched GEMM of one window (korder 6: chunk-major V and U' planes)
+pf_conv_params f16x2_points_params(const pf_conv_params* p, const void* U2, int u_rows, void* V2, float* M, long T) {
+  constexpr int A = 6;
+  pf_conv_params q = {};
+  q.x_ld = p->Cin; q.B = 1; q.H = 1; q.W = (int)T; q.Cin = p->Cin;
+  q.w_rows = u_rows; q.Kpad = p->Cin;
+  q.y_ld = p->Cout; q.OH = 1; q.OW = (int)T; q.Cout = p->Cout;
+  q.KH = q.KW = 1; q.stride = 1; q.pad = 0; q.act = PF_ACT_NONE; q.shuffle = 1; q.dtype = PF_DTYPE_BF16; q.out_f32 = 1;
+  q.x = V2; q.w = U2; q.y = M;
+  q.korder = 6;
+  q.batch = A * A;
+  q.x_bstride = (long)A * A * T * p->Cin;               // h / l plane strides
+  q.w_bstride = (long)A * A * u_rows * p->Cin;
+  return q;
+}
+
+int run_f16x2(const pf_conv_params* p, const float* U, int u_rows, void* V2, float* M, void* scratch, long window, hipStream_t st) {
+  constexpr int MT = 4;
+  const int TH = (p->H + MT - 1) / MT, TW = (p->W + MT - 1) / MT;
+  const long Tall = (long)p->B * TH * TW;
+  if (Tall > 0x7fffffffL) return PF_ERR_ARG;
+  if (window <= 0 || window > Tall) window = Tall;
+  if (window < Tall) {                                  // (the alias rule of run_split3)
+    const char* xa = static_cast<const char*>(p->x);
+    const char* ya = static_cast<const char*>(p->y);
+    const long xb = ((long)p->B * p->H * p->W - 1) * p->x_ld * 4 + (long)p->Cin * 4, yb = ((long)p->B * p->H * p->W - 1) * p->y_ld * 4 + (long)p->Cout * 4;
+    if (xa < ya + yb && ya < xa + xb) return PF_ERR_ARG;
+  }
+  const F16x2Scratch sc = f16x2_scratch(scratch, p->Cin, u_rows);
+  const float* x = static_cast<const float*>(p->x);
+  if (hipMemsetAsync(sc.cmax, 0, (size_t)p->Cin * 4, st) != hipSuccess) return PF_ERR_LAUNCH;
+  int rc = pf_f16x2::launch_absmax(x, p->x_ld, (long)p->B * p->H * p->W, p->Cin, p->relu_in, sc.cmax, st);
+  if (rc != PF_OK) return rc;
+  rc = pf_f16x2::launch_u_split(U, u_rows, p->Cin, sc.cmax, sc.u2, sc.fexp, st);
+  if (rc != PF_OK) return rc;
+  for (long t0 = 0; t0 < Tall; t0 += window) {
+    const long T = Tall - t0 < window ? Tall - t0 : window;
+    const long nout = T * (p->Cout / 4);
+    rc = pf_f16x2::launch_input(x, p->x_ld, p->B, p->H, p->W, p->Cin, p->relu_in, sc.cmax, V2, TH, TW, t0, T, st);
+    if (rc != PF_OK) return rc;
+    const pf_conv_params q = f16x2_points_params(p, sc.u2, u_rows, V2, M, T);
+    rc = pf_gemm_f16x2_points(&q, sc.fexp, 0, st);
+    if (rc != PF_OK) return rc;
+    hipLaunchKernelGGL(wino_output_kernel<MT>, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, M, p->Cout, p->bias, p->act == PF_ACT_RELU ? 1 : 0,
+                       static_cast<const float*>(p->res), p->res_ld, static_cast<const float*>(p->res2), p->res2_ld, static_cast<float*>(p->y), p->y_ld,
+                       p->B, p->H, p->W, TH, TW, t0, T);
+    if (launch_ok() != PF_OK) return PF_ERR_LAUNCH;
+  }
+  return PF_OK;
+}
+
+// the argument rules of pf_conv_winograd_split3_windowed (U = PackedConv.wino_u: float32 [36][u_rows][Cin])
+bool f16x2_args_ok(const pf_conv_params* p, int u_rows, int u_kpad, long window) {
+  if (!p || !p->x || !p->y || window < 0 || (window > 0 && window % 8)) return false;
+  if (p->dtype != PF_DTYPE_F32 || p->KH != 3 || p->KW != 3 || p->stride != 1 || p->pad != 1 || p->shuffle > 1 || p->scale) return false;
+  if (p->OH != p->H || p->OW != p->W || p->Cin % 32 || p->Cout % 8 || p->Cin <= 0 || p->Cout <= 0 || p->Cin > 8192) return false;
+  if (p->act != PF_ACT_NONE && p->act != PF_ACT_RELU) return false;
+  return u_rows >= p->Cout && u_rows % 16 == 0 && u_kpad == p->Cin;
+}
+
 }  // namespace
+
+extern "C" long pf_wino_f16x2_scratch_bytes(int cin, int u_rows) {
+  if (cin <= 0 || u_rows <= 0) return 0;
+  return (long)(align256((size_t)2 * 36 * u_rows * cin * 2) + align256((size_t)36 * u_rows * 4) + align256((size_t)cin * 4));
+}
+
+// 1 when the layer runs the fp16x2 product: the arguments qualify and the bf16x3 GEMM of the WHOLE layer (all tiles in one window) would take the
+// persistent 192 x 192 kernel, the only one with an fp16x2 form (the N = 256 layers stay on 128 x 128 tiles and on the bf16x3 route).  The decision
+// does not depend on the window, so every window size of a layer computes the same bits.
+extern "C" int pf_conv_winograd_f16x2_supported(const pf_conv_params* p, int u_rows, int u_kpad, long window) {
+  if (!f16x2_args_ok(p, u_rows, u_kpad, window)) return 0;
+  const long T = (long)p->B * ((p->H + 3) / 4) * ((p->W + 3) / 4);
+  if (T > 0x7fffffffL) return 0;
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  pf_conv_params q = f16x2_points_params(p, p->x, u_rows, const_cast<void*>(p->x), static_cast<float*>(p->y), T);
+  return pf_gemm_split3_route(&q, cus) == PF_S3_ROUTE_PERSIST192 ? 1 : 0;
+}
+
+extern "C" int pf_conv_winograd_f16x2_windowed(const pf_conv_params* p, const void* U, int u_rows, int u_kpad, void* V2, void* M, void* scratch,
+                                               long window, void* stream) {
+  if (!U || !V2 || !M || !scratch || !f16x2_args_ok(p, u_rows, u_kpad, window)) return PF_ERR_ARG;
+  return run_f16x2(p, static_cast<const float*>(U), u_rows, V2, static_cast<float*>(M), scratch, window, ST(stream));
+}
 
 extern "C" int pf_conv_winograd_split3(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, void* V3, void* M, void* stream) {
   if (!p || !U3 || !V3 || !M || !p->x || !p->y) return PF_ERR_ARG;

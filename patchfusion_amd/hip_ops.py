@@ -117,6 +117,12 @@ def _split3_three_step(pw):
     return pw.wino_u3 is not None and _env("PF_WINO_SPLIT3", "1") != "0"
 
 
+def _wino_f16x2_enabled():
+    """three-step split layers whose product runs on the 192 x 192 kernel take its fp16x2 form (csrc/wino_f16x2.hip: two fp16 planes per operand with
+    power-of-two channel / column scales, three MFMAs per product instead of six); PF_WINO_F16X2=0 keeps every layer on the bf16x3 planes"""
+    return _env("PF_WINO_F16X2", "1") != "0"
+
+
 def _fused_wanted(B, H, W, pw):
     """Fused Winograd kernel (csrc/wino_fused.hip) or the three-step form for this call?  PF_WINO_FUSED (read per call): 0 = never fused,
     2 = fused wherever supported, 1 (default) = the measured rule (profiles/r3_wino_fused_layers.log, r3_three_step_split.log; 1x MI355X):
@@ -143,6 +149,7 @@ def _fused_wanted(B, H, W, pw):
 
 
 _WS = {}
+_WS16 = {}
 
 
 def _workspace(device, nV, nM):
@@ -164,16 +171,28 @@ def _workspace(device, nV, nM):
     return v, m
 
 
+def _f16x2_scratch(device, nbytes):
+    """per-(device, stream) scratch of the fp16x2 Winograd layers: channel maxima, scaled filter planes, column exponents (rewritten by every call)"""
+    key = (device.index, torch.cuda.current_stream().cuda_stream)
+    t = _WS16.get(key)
+    if t is None or t.numel() < nbytes:
+        _WS16.pop(key, None)
+        t = None
+        t = _WS16[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return t
+
+
 def release_workspaces():
     """free the per-(device, stream) Winograd arenas (at the headline layer 12 GB + 8 GB per stream); they are re-grown on demand.  Also drops the
     cached dispatch plans: they hold strong references to the packed layers (device weights + Winograd filter planes, several GB for ViT-L), so
     `del model; release_workspaces(); torch.cuda.empty_cache()` really returns the memory (round-4 advisor finding)"""
     _WS.clear()
+    _WS16.clear()
     _CONV_CACHE.clear()
 
 
 def workspace_bytes():
-    return sum(v.numel() * 4 + m.numel() * 4 for v, m in _WS.values())
+    return sum(v.numel() * 4 + m.numel() * 4 for v, m in _WS.values()) + sum(t.numel() for t in _WS16.values())
 
 
 def _fused_group():
@@ -216,7 +235,7 @@ class HipOps:
     @staticmethod
     def _conv_plan(x, pw, y, stride, pad, act, relu_in, res, res2, direct):
         """everything about a conv call that does not change while shapes / strides / the packed layer stay the same: the argument checks, the filled
-        pf_conv_params and the dispatch decision ('pp' | 'fused' | 'wino3' | 'wino' | 'direct').  Cached by HipOps.conv per (layer, layout)."""
+        pf_conv_params and the dispatch decision ('pp' | 's3_1x1' | 'fused' | 'wino3h' | 'wino3' | 'wino' | 'direct').  Cached by HipOps.conv per (layer, layout)."""
         x4, y4 = _as4(x), _as4(y)
         B, H, W, _ = x4.shape
         OH = (H + 2 * pad - pw.KH) // stride + 1
@@ -266,6 +285,10 @@ class HipOps:
             if m == 4 and _split3_three_step(pw):
                 # (split: V holds three bf16 planes = 6 bytes per element instead of 4; whole tile octets, csrc/winograd.hip)
                 window, _, nV, nM = wino3_window(B, H, W, pw)
+                rows, kpad = pw.wino_u.shape[1], pw.wino_u.shape[2]
+                if _wino_f16x2_enabled() and _L.pf_conv_winograd_f16x2_supported(C.byref(p), rows, kpad, window):
+                    # fp16x2 planes (the same windows; V: two fp16 planes = one float32 word per element)
+                    return "wino3h", p, (_p(pw.wino_u), rows, kpad, 36 * window * pw.cin, nM, window, _L.pf_wino_f16x2_scratch_bytes(pw.cin, rows))
                 return "wino3", p, (_p(pw.wino_u3), pw.wino_u3.shape[3], pw.wino_u3.shape[2] * 32, nV, nM, window)
             return "wino", p, (m, _p(pw.wino_u), pw.wino_u.shape[1], pw.wino_u.shape[2], a2 * T * pw.cin, a2 * T * pw.cout)
         return "direct", p, None          # (incl. fused-only layers below the block threshold)
@@ -282,6 +305,11 @@ class HipOps:
             V, Mw = _workspace(device, extra[3], extra[4])
             check(_L.pf_conv_winograd_split3_windowed(C.byref(p), extra[0], extra[1], extra[2], C.c_void_p(V.data_ptr()), C.c_void_p(Mw.data_ptr()),
                                                       extra[5], _stream()), "pf_conv_winograd_split3_windowed")
+        elif route == "wino3h":
+            V, Mw = _workspace(device, extra[3], extra[4])
+            S = _f16x2_scratch(device, extra[6])
+            check(_L.pf_conv_winograd_f16x2_windowed(C.byref(p), extra[0], extra[1], extra[2], C.c_void_p(V.data_ptr()), C.c_void_p(Mw.data_ptr()),
+                                                     C.c_void_p(S.data_ptr()), extra[5], _stream()), "pf_conv_winograd_f16x2_windowed")
         elif route == "wino":
             V, Mw = _workspace(device, extra[4], extra[5])
             check(_L.pf_conv_winograd(C.byref(p), extra[0], extra[1], extra[2], extra[3], C.c_void_p(V.data_ptr()), C.c_void_p(Mw.data_ptr()), _stream()),
