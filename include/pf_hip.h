@@ -60,6 +60,8 @@ typedef struct {
                     x + k*x_bstride, w + k*w_bstride and writes y + k*y_bstride (strides in elements); 0 / 1 = a single plane.
                     Used for the (m+2)^2 transform points of a Winograd layer (pf_conv_winograd). */
   long x_bstride, w_bstride, y_bstride;
+  const int* col_exp;  /* fp16x2 linears only (pf_gemm_f16x2): int32 column exponents f_n [w_rows], y = ldexp(acc, f_n) before the epilogue */
+  const int* out_exp;  /* fp16x2 linears with fp16x2 planes out: int32 exponents of the consumer's input channels [Cout] */
 } pf_conv_params;
 int pf_conv(const pf_conv_params* p, void* stream);
 /* timing helper for the roofline entry of bench.py: runs `iters` launches bracketed by HIP events on
@@ -96,6 +98,13 @@ int pf_conv_winograd_f16x2_windowed(const pf_conv_params* p, const void* U, int 
 /* its batched product alone: x / w = two fp16 planes each, chunk-major (korder = 6, batch = transform points, no epilogue), y float32 =
  * ldexp(sum, col_exp[z][n]) with col_exp int32 [batch][w_rows] */
 int pf_gemm_f16x2_points(const pf_conv_params* p, const int* col_exp, int grid_cap, void* stream);
+/* fp16x2 linear layer (the ViT block linears; packing.pack_conv_f16x2): x = two fp16 planes, chunk-major [2][K/32][M][32], holding x / 2^e_k;
+ * w = two fp16 planes [2][K/32][w_rows][32] holding W[n][k] 2^(e_k - f_n); korder must be 6 (| 16, see below).  p->col_exp = f_n [w_rows] (required).
+ * The persistent 192 x 192 kernel sums the three products hh, hl, lh in float32, applies ldexp(acc, f_n) and then the pf_conv epilogue
+ * (bias -> act -> scale -> res -> res2, all float32), and stores one of: float32 [M][y_ld] (out_f32); three bf16 planes, row-major [3][M][y_ld]
+ * (y_bstride); or, with korder bit 16, two fp16 chunk-major planes [2][Cout/32][M][32] of y / 2^out_exp[n] (y_ld == Cout, Cout % 32 == 0,
+ * p->out_exp required).  No batch. */
+int pf_gemm_f16x2(const pf_conv_params* p, void* stream);
 
 /* FUSED Winograd F(4x4, 3x3) (csrc/wino_fused.hip): the same layers in ONE kernel -- the transformed input and the transform-domain
  * products never exist in HBM.  `p` as for pf_conv_winograd (p->w is not read); `up` = the filters in MFMA fragment order
@@ -150,6 +159,10 @@ int pf_gemm_bf16_pp(const pf_conv_params* p, void* stream);
  * korder bit 1; kmajor == 0: row-major [rows][ld]. */
 int pf_layernorm_split3(const float* x, int x_ld, void* y3, int y_ld, long plane, int kmajor, const float* g, const float* b, float eps,
                         long rows, int D, void* stream);
+/* LayerNorm as the fp16x2 input of pf_gemm_f16x2: y2 = two fp16 planes, chunk-major [2][D/32][rows][32] (plane = rows * D elements), holding
+ * LN(x)[k] / 2^in_exp[k] as h + l (in_exp: int32 [D], packing.pack_conv_f16x2 of the consuming linear) */
+int pf_layernorm_f16x2(const float* x, int x_ld, void* y2, const int* in_exp, const float* g, const float* b, float eps, long rows, int D,
+                       void* stream);
 int pf_vit_attention_qkv_split3(const void* qkv, void* out3, long plane, int kmajor, int B, int S, int Hh, void* stream);
 /* The same attention entirely in split precision: qkv3 = the QKV GEMM's output as three bf16 planes [3][B*S][3*Hh*64] (plane stride plane_in
  * elements), out3 = three bf16 planes [3][B*S][Hh*64] (plane_out); S^T = K.Q^T and O^T = V^T.P^T as six bf16 partial products each with float32

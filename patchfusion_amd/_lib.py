@@ -29,6 +29,7 @@ class ConvParams(C.Structure):
         ("KH", ci), ("KW", ci), ("stride", ci), ("pad", ci),
         ("act", ci), ("relu_in", ci), ("out_f32", ci), ("shuffle", ci), ("dtype", ci), ("korder", ci),
         ("batch", ci), ("x_bstride", C.c_long), ("w_bstride", C.c_long), ("y_bstride", C.c_long),
+        ("col_exp", vp), ("out_exp", vp),
     ]
 
 
@@ -59,6 +60,7 @@ SIGNATURES = {
     "pf_conv_winograd_split3_windowed": [C.POINTER(ConvParams), vp, ci, ci, vp, vp, C.c_long, vp],
     "pf_conv_winograd_f16x2_windowed": [C.POINTER(ConvParams), vp, ci, ci, vp, vp, vp, C.c_long, vp],
     "pf_gemm_f16x2_points": [C.POINTER(ConvParams), vp, ci, vp],
+    "pf_gemm_f16x2": [C.POINTER(ConvParams), vp],
     "pf_gemm_split3": [C.POINTER(ConvParams), vp],
     "pf_gemm_split3_ex": [C.POINTER(ConvParams), ci, vp],
     "pf_conv1x1_split3": [C.POINTER(ConvParams), vp, ci, vp],
@@ -66,6 +68,7 @@ SIGNATURES = {
     "pf_gemm_bf16_pp": [C.POINTER(ConvParams), vp],
     "pf_split3": [vp, ci, vp, ci, cl, cl, ci, vp],
     "pf_layernorm_split3": [vp, ci, vp, ci, cl, ci, vp, vp, cf, cl, ci, vp],
+    "pf_layernorm_f16x2": [vp, ci, vp, vp, vp, vp, cf, cl, ci, vp],
     "pf_vit_attention_qkv_split3": [vp, vp, cl, ci, ci, ci, ci, vp],
     "pf_vit_attention_split3": [vp, cl, vp, cl, ci, ci, ci, ci, vp],
     "pf_vit_attention_split3_v2": [vp, cl, vp, cl, ci, ci, ci, ci, ci, ci, vp],

@@ -64,7 +64,7 @@ class BaselinePretrain(PatchFusion):
             if self.branch_cfg.type == 'ZoeDepth':
                 net = ExternalCoreBranchNet(sd, self.prefix, self.branch_cfg, self.patch_process_shape, self.compute_dtype, dev, self.core_provider)
             else:
-                net = BranchNet(sd, self.prefix, self.branch_cfg, self.patch_process_shape, self.compute_dtype, dev)
+                net = BranchNet(sd, self.prefix, self.branch_cfg, self.patch_process_shape, self.compute_dtype, dev, ops=self.ops, crops=True)
             self._engine = dict(branch=net)
             self._device, self._mask_cache, self._table_cache = dev, {}, {}
         return self._engine

@@ -633,9 +633,13 @@ __global__ __launch_bounds__(512) void gemm_split3_persist_kernel(const pf_conv_
 // newest vector-memory operations of the wave are then its pieces of chunk g+2, issued after those of g+1.  Only DMA pieces are counted against DMA
 // pieces -- the epilogue's register loads and stores of the wave sit OLDER than chunk g+2's pieces, so however they retire relative to the pieces
 // they cannot make the count pass early (the DESIGN 4i rule: never count register loads in a hand-counted wait).
+// F16 && !BARE (round 8, the ViT block linears, pf_gemm_f16x2): the same ring with the full epilogue.  The column exponents come from p.col_exp
+// (p.scale is LayerScale there); ldexp(acc, f_n) first, then bias -> act -> scale -> residual(s), stored as float32, as three bf16 row-major planes,
+// or (korder bit 16) as two fp16 chunk-major planes of y / 2^out_exp[n] for a following fp16x2 linear (fc1 -> fc2).  The epilogue still runs at the
+// head of a load phase, before that phase's pieces: its bias / scale / exponent / residual loads and its stores are older than the pieces each
+// counted wait lets fly, exactly as the BARE form's exponent loads are.
 template <bool BARE, bool BL, bool F16 = false, int NSL = 2>
 __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_conv_params p, int mt, int nt, int gm, int total, int flags) {
-  static_assert(!F16 || BARE, "fp16x2: batched transform-domain GEMM only");
   static_assert(NSL == 2 || (NSL == 3 && BL), "three ring slots: the BL schedule only");
   constexpr int BM = 192, BN = 192, WM = 4, WN = 2, NP = F16 ? 2 : 3, NS = NSL, NTERM = F16 ? 3 : 6, LEAD = NS - 1;
   constexpr int NW = WM * WN;
@@ -828,9 +832,12 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
       const int n = e_n0 + wn * e_wtn + fsel * 16 + fg * 4;
       const bool nok = n < p.Cout && fsel < e_nfn;
       float4 bias_r = make_float4(0.f, 0.f, 0.f, 0.f), scale_r = make_float4(1.f, 1.f, 1.f, 1.f);
-      int4 fexp = make_int4(0, 0, 0, 0);
-      if constexpr (F16) {
+      int4 fexp = make_int4(0, 0, 0, 0), oexp = make_int4(0, 0, 0, 0);
+      if constexpr (F16 && BARE) {
         if (nok) fexp = *reinterpret_cast<const int4*>(reinterpret_cast<const int*>(p.scale) + (long)e_z * p.w_rows + n);
+      } else if constexpr (F16) {
+        if (nok) fexp = *reinterpret_cast<const int4*>(p.col_exp + n);
+        if (nok && (p.korder & 16)) oexp = *reinterpret_cast<const int4*>(p.out_exp + n);
       }
       if constexpr (!BARE) {
         if (nok) {
@@ -894,7 +901,23 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
             }
             if (p.out_f32) {
               if (ok) *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.y) + y_base + (long)m * p.y_ld + n) = make_float4(v[h][0], v[h][1], v[h][2], v[h][3]);
-            } else if (!(p.korder & 8)) {
+            } else if (F16 && (p.korder & 16)) {
+              // two fp16 planes of y / 2^out_exp (chunk-major): swap(h, l) leaves the even 4-channel group with 16 bytes of plane h, the odd one
+              // with 16 bytes of plane l (the pairing of the three-plane store below)
+              const int oe[4] = {oexp.x, oexp.y, oexp.z, oexp.w};
+              uint32_t hw[2], lw2[2];
+#pragma unroll
+              for (int r = 0; r < 4; r += 2) {
+                const float t0 = ldexpf(v[h][r], -oe[r]), t1 = ldexpf(v[h][r + 1], -oe[r + 1]);
+                const _Float16 h0 = (_Float16)t0, h1 = (_Float16)t1;
+                const _Float16 l0 = (_Float16)(t0 - (float)h0), l1 = (_Float16)(t1 - (float)h1);
+                hw[r >> 1] = (uint32_t)__builtin_bit_cast(uint16_t, h0) | ((uint32_t)__builtin_bit_cast(uint16_t, h1) << 16);
+                lw2[r >> 1] = (uint32_t)__builtin_bit_cast(uint16_t, l0) | ((uint32_t)__builtin_bit_cast(uint16_t, l1) << 16);
+              }
+              const auto s0 = __builtin_amdgcn_permlane16_swap(hw[0], lw2[0], false, false);
+              const auto s1 = __builtin_amdgcn_permlane16_swap(hw[1], lw2[1], false, false);
+              if (ok) *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(p.y) + split3_at(m, ne, p.y_ld, M) + (oddg ? p.y_bstride : 0)) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+            } else if (F16 || !(p.korder & 8)) {
               if (ok) store_split3(reinterpret_cast<bf16_t*>(p.y) + split3_at(m, n, p.y_ld, 0), p.y_bstride, v[h]);
             } else {
               uint32_t h0, m0, h1, mm1;
@@ -906,7 +929,7 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
               if (ok) *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.y) + split3_at(m, ne, p.y_ld, M) + (oddg ? p.y_bstride : 0)) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
             }
           }
-          if (!p.out_f32 && (p.korder & 8)) {
+          if (!F16 && !p.out_f32 && (p.korder & 8)) {
             const auto t0 = __builtin_amdgcn_permlane16_swap(lw[0][0], lw[1][0], false, false);
             const auto t1 = __builtin_amdgcn_permlane16_swap(lw[0][1], lw[1][1], false, false);
             const int ml = m1 + (oddg ? 8 : 0);
@@ -1187,6 +1210,31 @@ int launch_persist192_f16(const pf_conv_params& p, hipStream_t st, int grid_cap)
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
 }
 
+// the fp16x2 linear (one plane, full epilogue) on the three-slot ring.  Fewer than 8 tiles: 8 blocks anyway (every XCD needs a block for the walk;
+// the blocks of an empty tile range return at once).
+int launch_persist192_f16_linear(const pf_conv_params& p, hipStream_t st) {
+  constexpr int smem = 3 * 2 * (192 + 192) * 64;
+  static std::atomic<unsigned long long> done{0};
+  int dev = 0;
+  hipGetDevice(&dev);
+  const unsigned long long bit = 1ull << (dev & 63);
+  if (!(done.load(std::memory_order_acquire) & bit)) {
+    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3_persist192_kernel<false, true, true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    done.fetch_or(bit, std::memory_order_release);
+  }
+  const long M = (long)p.B * p.OH * p.OW;
+  const int mt = (int)((M + 191) / 192), nt = (p.Cout + 191) / 192;
+  const long total = (long)mt * nt;
+  const int gm = tile_group(nt);
+  int grid = cu_count();
+  if (grid > total) grid = (int)total;
+  grid &= ~7;
+  if (grid < 8) grid = 8;
+  if (total > 0x7fffffffL) return PF_ERR_ARG;
+  hipLaunchKernelGGL((gemm_split3_persist192_kernel<false, true, true, 3>), dim3((unsigned)grid), dim3(512), smem, st, p, mt, nt, gm, (int)total, 8);
+  return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
+}
+
 template <int BM, int BN, int WM, int WN, int NS, bool PP = false, int NP = 3, bool PLAIN = false>
 int launch(const pf_conv_params& p, hipStream_t st) {
   constexpr int smem = NS * NP * (BM + BN) * 64;
@@ -1308,6 +1356,22 @@ extern "C" int pf_gemm_f16x2_points(const pf_conv_params* p, const int* col_exp,
   pf_conv_params q = *p;
   q.scale = reinterpret_cast<const float*>(col_exp);     // (int32 exponents; the kernel's F16 epilogue reads them as such)
   return launch_persist192_f16(q, reinterpret_cast<hipStream_t>(stream), grid_cap);
+}
+
+// fp16x2 linear layer (include/pf_hip.h pf_gemm_f16x2; the ViT block linears, packing.pack_conv_f16x2)
+extern "C" int pf_gemm_f16x2(const pf_conv_params* p, void* stream) {
+  if (!p || !p->x || !p->w || !p->y || !p->col_exp) return PF_ERR_ARG;
+  const long M = (long)p->B * p->OH * p->OW;
+  if (p->KH != 1 || p->KW != 1 || p->stride != 1 || p->pad != 0 || p->shuffle > 1 || p->batch > 1 || (p->korder & ~16) != 6) return PF_ERR_ARG;
+  if (p->Cin <= 0 || p->Cin % 32 || p->x_ld != p->Cin || p->Kpad != p->Cin || p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || p->w_rows < p->Cout ||
+      p->w_rows % 4)
+    return PF_ERR_ARG;
+  if (M <= 0 || M * 64 >= (1L << 31) || (long)p->w_rows * 64 >= (1L << 31) || p->x_bstride <= 0 || p->w_bstride <= 0) return PF_ERR_ARG;
+  if ((p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) return PF_ERR_ARG;
+  if (p->out_f32 && (p->korder & 16)) return PF_ERR_ARG;
+  if (!p->out_f32 && p->y_bstride <= 0) return PF_ERR_ARG;
+  if ((p->korder & 16) && (!p->out_exp || p->y_ld != p->Cout || p->Cout % 32)) return PF_ERR_ARG;
+  return launch_persist192_f16_linear(*p, reinterpret_cast<hipStream_t>(stream));
 }
 
 // plain bf16 linear layer through the ping-pong pipeline (see the PLAIN template parameter): x [M][x_ld] bf16, w [w_rows][Kpad] bf16

@@ -141,6 +141,64 @@ __global__ __launch_bounds__(256) void layernorm_split3_kernel(const float* __re
   }
 }
 
+// LayerNorm of float32 rows as the fp16x2 input of the ViT block linears (csrc/gemm_split3.hip pf_gemm_f16x2): the row statistics of
+// layernorm_split3_kernel, then t = LN(x)[k] / 2^e_k (exact: a power of two), h = fp16_rn(t), l = fp16_rn(t - h), two chunk-major planes
+// [2][D/32][rows][32].  e_k comes from the static bound |LN(x)[k]| <= |g_k| sqrt(D - 1) + |b_k| (packing.pack_conv_f16x2): |t| <= 2^14.
+__global__ __launch_bounds__(256) void layernorm_f16x2_kernel(const float* __restrict__ x, int x_ld, uint16_t* __restrict__ y, const int* __restrict__ ex,
+                                                              const float* __restrict__ g, const float* __restrict__ bta, float eps, long rows, int D) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float* xr = x + row * x_ld;
+  const int nv = D >> 3;
+  const long plane = rows * D;
+  float v[4][8];
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int vi = lane + 64 * i;
+    if (vi < nv) {
+      load8(xr + vi * 8, v[i]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s += v[i][e];
+    }
+  }
+  const float mean = wave_sum(s) / D;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int vi = lane + 64 * i;
+    if (vi < nv) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { const float d = v[i][e] - mean; q += d * d; }
+    }
+  }
+  const float rstd = rsqrtf(wave_sum(q) / D + eps);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int vi = lane + 64 * i;
+    if (vi < nv) {
+      uint32_t hw[4], lw[4];
+#pragma unroll
+      for (int e = 0; e < 8; e += 2) {
+        float t[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int k = vi * 8 + e + u;
+          t[u] = ldexpf((v[i][e + u] - mean) * rstd * g[k] + bta[k], -ex[k]);
+        }
+        const _Float16 h0 = (_Float16)t[0], h1 = (_Float16)t[1];
+        const _Float16 l0 = (_Float16)(t[0] - (float)h0), l1 = (_Float16)(t[1] - (float)h1);
+        hw[e >> 1] = (uint32_t)__builtin_bit_cast(uint16_t, h0) | ((uint32_t)__builtin_bit_cast(uint16_t, h1) << 16);
+        lw[e >> 1] = (uint32_t)__builtin_bit_cast(uint16_t, l0) | ((uint32_t)__builtin_bit_cast(uint16_t, l1) << 16);
+      }
+      uint16_t* yo = y + split3_at(row, vi * 8, D, rows);
+      *reinterpret_cast<uint4*>(yo) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
+      *reinterpret_cast<uint4*>(yo + plane) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // qkv split: qkv [B*S][3][Hh][64] -> Q*scale [B,Hh,S,64], K [B,Hh,S,64], V^T [B,Hh,64,Sp]
 // grid (ceil(S/64), B*Hh), 256 threads.
@@ -1024,6 +1082,13 @@ extern "C" int pf_layernorm_split3(const float* x, int x_ld, void* y3, int y_ld,
   if (kmajor && (D % 32 || y_ld != D)) return PF_ERR_ARG;                        // chunk-major planes are dense: [D/32][rows][32]
   hipLaunchKernelGGL(layernorm_split3_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ST(stream), x, x_ld, (bf16_t*)y3, y_ld, plane, g, b, eps, rows, D,
                      kmajor ? rows : 0L);
+  return ok();
+}
+
+extern "C" int pf_layernorm_f16x2(const float* x, int x_ld, void* y2, const int* in_exp, const float* g, const float* b, float eps, long rows, int D,
+                                  void* stream) {
+  if (!x || !y2 || !in_exp || !g || !b || D % 32 || D > 2048 || x_ld % 8 || x_ld < D || rows <= 0) return PF_ERR_ARG;
+  hipLaunchKernelGGL(layernorm_f16x2_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ST(stream), x, x_ld, (uint16_t*)y2, in_exp, g, b, eps, rows, D);
   return ok();
 }
 

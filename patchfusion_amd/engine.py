@@ -31,6 +31,16 @@ def linear_split3_enabled():
     return os.environ.get("PF_LINEAR_SPLIT3", "1") != "0"
 
 
+def vit_f16x2_enabled(crops):
+    """float32 mode with split-precision linears: run qkv / fc1 / fc2 of the ViT blocks on two scaled fp16 planes (packing.pack_conv_f16x2,
+    csrc/gemm_split3.hip pf_gemm_f16x2: three MFMAs per product instead of six)?  Read once per engine build.  PF_VIT_F16X2: 0 = never,
+    2 = every branch, 1 (default) = the branch that runs batches of crops.  Measured per launch (profiles/r8_vit_f16x2_linears.md): at 8 x 1037
+    tokens 1.22-1.52x, at the coarse branch's single image (1037 tokens: 36-132 tiles of 192 x 192 on 256 CUs) 0.36-0.93x."""
+    import os
+    v = os.environ.get("PF_VIT_F16X2", "1")
+    return v == "2" or (v != "0" and crops)
+
+
 def attention_split3_enabled():
     """float32 mode with split-precision linears: also run the ViT attention in split precision (pf_vit_attention_split3)?  PF_ATTN_SPLIT3=0 / 1"""
     import os
@@ -161,7 +171,7 @@ class BinsHead:
 class BranchNet:
     """One ZoeDepth branch with a Depth-Anything (DINOv2 ViT + DPT) core."""
 
-    def __init__(self, sd, prefix, bcfg, process_shape, dtype, device):
+    def __init__(self, sd, prefix, bcfg, process_shape, dtype, device, ops=None, crops=False):
         self.dtype, self.device = dtype, device
         enc = bcfg["midas_model_type"]
         self.D, self.depth, self.heads = VIT_ARCH[enc]
@@ -189,16 +199,31 @@ class BranchNet:
                 if ".blocks." in name:
                     return pk.pack_conv_split3(sd[name + ".weight"], sd[name + ".bias"] if bias else None, **kw).to(dev)
                 return _pc(name, bias, **kw)
+        # ... and, when the op set has the fp16x2 linears (the HIP ops do; PF_VIT_F16X2=0 keeps bf16x3), qkv / fc1 / fc2 run on two fp16 planes
+        # with static power-of-two scales derived from the weights (packing.pack_conv_f16x2): only those planes are packed for them.  The
+        # projection keeps the bf16x3 planes the attention writes.
+        # (crops: this branch runs batches of crops -- the fine branch -- rather than one image per call)
+        self.f16x2 = self.split3 and vit_f16x2_enabled(crops) and getattr(ops, "conv_f16x2", None) is not None
         self.blocks = []
         for i in range(self.depth):
             b = f"{v}blocks.{i}."
+            n1, n2 = (sd[b + "norm1.weight"], sd[b + "norm1.bias"]), (sd[b + "norm2.weight"], sd[b + "norm2.bias"])
+            if self.f16x2:
+                bn1, bn2 = pk.layernorm_bound(*n1), pk.layernorm_bound(*n2)
+                w1, b1 = sd[b + "mlp.fc1.weight"], sd[b + "mlp.fc1.bias"]
+                qkv = pk.pack_conv_f16x2(sd[b + "attn.qkv.weight"], sd[b + "attn.qkv.bias"], None, bn1).to(dev)
+                fc1 = pk.pack_conv_f16x2(w1, b1, None, bn2).to(dev)
+                fc2 = pk.pack_conv_f16x2(sd[b + "mlp.fc2.weight"], sd[b + "mlp.fc2.bias"], sd[b + "ls2.gamma"],
+                                         pk.gelu_linear_bound(w1, b1, bn2)).to(dev)
+            else:
+                qkv, fc1, fc2 = pc(b + "attn.qkv"), pc(b + "mlp.fc1"), pc(b + "mlp.fc2", scale=sd[b + "ls2.gamma"])
             self.blocks.append(dict(
                 n1=(_g(sd, b + "norm1.weight", dev), _g(sd, b + "norm1.bias", dev)),
-                qkv=pc(b + "attn.qkv"),
+                qkv=qkv,
                 proj=pc(b + "attn.proj", scale=sd[b + "ls1.gamma"]),
                 n2=(_g(sd, b + "norm2.weight", dev), _g(sd, b + "norm2.bias", dev)),
-                fc1=pc(b + "mlp.fc1"),
-                fc2=pc(b + "mlp.fc2", scale=sd[b + "ls2.gamma"])))
+                fc1=fc1,
+                fc2=fc2))
         self.norm = (_g(sd, v + "norm.weight", dev), _g(sd, v + "norm.bias", dev))
         self.projects = [pc(f"{h}projects.{i}") for i in range(4)]
         self.up4 = pk.pack_conv_transpose(sd[h + "resize_layers.0.weight"], sd[h + "resize_layers.0.bias"], dtype=dtype).to(dev)
@@ -263,13 +288,23 @@ class BranchNet:
                 hbuf, att, mid = (ops.empty((3, B * S, n), torch.bfloat16, dev) for n in (D, D, 4 * D))
             # ... and so do q / k / v (row-major: the attention kernel reads token rows): attention in split precision (csrc/vit.hip)
             qkv = ops.empty((3, B * S, 3 * D), torch.bfloat16, dev) if attention_split3_enabled() else ops.empty((B * S, 3 * D), dt, dev)
+            if self.f16x2:                                         # LayerNorm outputs and the fc1 -> fc2 intermediate as two fp16 planes, chunk-major
+                hbuf, mid = (ops.empty((2, n // 32, B * S, 32), torch.float16, dev) for n in (D, 4 * D))
         else:
             hbuf = ops.empty((B * S, D), dt, dev)
             qkv = ops.empty((B * S, 3 * D), dt, dev)
             att = ops.empty((B * S, D), dt, dev)
             mid = ops.empty((B * S, 4 * D), dt, dev)
         for i, blk in enumerate(self.blocks):
-            if self.split3:
+            if self.f16x2:
+                ops.layernorm_f16x2(x, hbuf, blk["n1"][0], blk["n1"][1], 1e-6, blk["qkv"].in_exp)
+                ops.conv_f16x2(hbuf, blk["qkv"], qkv)
+                ops.vit_attention(qkv, att, B, S, self.heads)
+                ops.conv_split3(att, blk["proj"], x, res=x)
+                ops.layernorm_f16x2(x, hbuf, blk["n2"][0], blk["n2"][1], 1e-6, blk["fc1"].in_exp)
+                ops.conv_f16x2(hbuf, blk["fc1"], mid, act="gelu", out_exp=blk["fc2"].in_exp)
+                ops.conv_f16x2(mid, blk["fc2"], x, res=x)
+            elif self.split3:
                 ops.layernorm_split3(x, hbuf, blk["n1"][0], blk["n1"][1], 1e-6)
                 ops.conv_split3(hbuf, blk["qkv"], qkv)
                 ops.vit_attention(qkv, att, B, S, self.heads)

@@ -501,6 +501,67 @@ class HipOps:
         check(_L.pf_gemm_split3(C.byref(p), _stream()), "pf_gemm_split3")
         return y
 
+    @staticmethod
+    def _conv_f16x2_plan(x2, pw, y, act, res, res2, out_exp):
+        assert x2.dtype == pw.w.dtype == torch.float16 and x2.dim() == 4 and x2.shape[0] == 2 and x2.shape[3] == 32 and x2.is_contiguous()
+        assert x2.shape[1] * 32 == pw.cin and pw.w.dim() == 4 and pw.w.is_contiguous() and pw.col_exp is not None
+        M = x2.shape[2]
+        p = ConvParams()
+        p.x, p.x_ld, p.x_bstride = x2.data_ptr(), pw.cin, x2.stride(0)
+        p.B, p.H, p.W, p.Cin = 1, 1, M, pw.cin
+        p.w, p.w_rows, p.Kpad, p.w_bstride = pw.w.data_ptr(), pw.w.shape[2], pw.cin, pw.w.stride(0)
+        p.bias = pw.bias.data_ptr() if pw.bias is not None else None
+        p.scale = pw.scale.data_ptr() if pw.scale is not None else None
+        p.col_exp = _p(pw.col_exp)
+        p.res = res.data_ptr() if res is not None else None
+        p.res_ld = res.stride(-2) if res is not None else 0
+        p.res2 = res2.data_ptr() if res2 is not None else None
+        p.res2_ld = res2.stride(-2) if res2 is not None else 0
+        korder = 6
+        if y.dtype == torch.float16:                          # fp16x2 planes of y / 2^out_exp for the next fp16x2 linear, chunk-major [2, N/32, M, 32]
+            assert y.is_contiguous() and tuple(y.shape) == (2, pw.cout // 32, M, 32) and pw.cout % 32 == 0
+            assert out_exp is not None and out_exp.dtype == torch.int32 and out_exp.numel() >= pw.cout
+            p.y, p.y_ld, p.y_bstride, p.out_f32, p.out_exp = y.data_ptr(), pw.cout, y.stride(0), 0, _p(out_exp)
+            korder |= 16
+        elif y.dtype == torch.bfloat16:                       # three bf16 planes, row-major [3, M, N] (the attention's q / k / v)
+            assert y.dim() == 3 and y.shape[0] == 3 and y.shape[1] == M and y.stride(2) == 1 and y.shape[2] >= pw.cout
+            p.y, p.y_ld, p.y_bstride, p.out_f32 = y.data_ptr(), y.stride(1), y.stride(0), 0
+        else:
+            assert y.dtype == torch.float32 and y.stride(-1) == 1 and y.shape[-2] == M and y.shape[-1] >= pw.cout
+            p.y, p.y_ld, p.out_f32 = y.data_ptr(), y.stride(-2), 1
+        p.OH, p.OW, p.Cout = 1, M, pw.cout
+        p.KH = p.KW = p.stride = 1
+        p.act, p.shuffle, p.dtype, p.korder = ACT[act], 1, 1, korder
+        for t in (x2, y, pw.w, res, res2):
+            _p(t)
+        for t in (res, res2):
+            assert t is None or (t.dtype == torch.float32 and t.shape[-1] >= pw.cout and t.shape[-2] == M), "residuals are float32 [M, >= N]"
+        return p
+
+    @staticmethod
+    def conv_f16x2(x2, pw: PackedConv, y, act=None, res=None, res2=None, out_exp=None):
+        """x2 float16 planes [2, K/32, M, 32] holding x / 2^pw.in_exp (ops.layernorm_f16x2 or a previous conv_f16x2); pw from packing.pack_conv_f16x2;
+        y float32 [M, N], bfloat16 [3, M, N] (three split planes, row-major) or float16 [2, N/32, M, 32] (planes of y / 2^out_exp for the next
+        fp16x2 linear); res / res2 float32 [M, N].  csrc/gemm_split3.hip pf_gemm_f16x2; plans cached like conv_split3."""
+        key = ("f16x2", id(pw), x2.shape, y.shape, y.stride(), y.dtype, act, x2.device,
+               None if res is None else (res.shape, res.stride()), None if res2 is None else (res2.shape, res2.stride()),
+               None if out_exp is None else out_exp.data_ptr())
+        ent = _CONV_CACHE.get(key)
+        if ent is None or ent[0] is not pw:
+            if len(_CONV_CACHE) > 4096:
+                _CONV_CACHE.clear()
+            ent = (pw, HipOps._conv_f16x2_plan(x2, pw, y, act, res, res2, out_exp))
+            _CONV_CACHE[key] = ent
+        else:
+            p = ent[1]
+            p.x, p.y = x2.data_ptr(), y.data_ptr()
+            if res is not None:
+                p.res = res.data_ptr()
+            if res2 is not None:
+                p.res2 = res2.data_ptr()
+        check(_L.pf_gemm_f16x2(C.byref(ent[1]), _stream()), "pf_gemm_f16x2")
+        return y
+
     # ---------------- ViT ----------------
     @staticmethod
     def patch_im2col(img, out):
@@ -539,6 +600,15 @@ class HipOps:
         check(_L.pf_layernorm_split3(_p(x), x.stride(0), _p(y3), y3.stride(1), y3.stride(0), 0, _p(g), _p(b), float(eps), M, D, _stream()),
               "pf_layernorm_split3")
         return y3
+
+    @staticmethod
+    def layernorm_f16x2(x, y2, g, b, eps, in_exp):
+        """LayerNorm of float32 rows x [M, D] as the fp16x2 input of ops.conv_f16x2: y2 float16 [2, D/32, M, 32] = LN(x) / 2^in_exp split h + l"""
+        assert x.dtype == torch.float32 and x.stride(-1) == 1 and y2.dtype == torch.float16 and in_exp.dtype == torch.int32
+        M, D = x.shape
+        assert y2.is_contiguous() and tuple(y2.shape) == (2, D // 32, M, 32) and in_exp.numel() == D
+        check(_L.pf_layernorm_f16x2(_p(x), x.stride(0), _p(y2), _p(in_exp), _p(g), _p(b), float(eps), M, D, _stream()), "pf_layernorm_f16x2")
+        return y2
 
     @staticmethod
     def vit_attention(qkv, out, B, S, heads):

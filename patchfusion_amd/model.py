@@ -353,13 +353,13 @@ class PatchFusion(nn.Module, PyTorchModelHubMixin):
                 raise RuntimeError("PatchFusion (MI355X engine) needs the model on a GPU: call .cuda() first")
             dt, cfg = self.compute_dtype, self.config
             self._forget_engine_state()                       # PF_* switches are resolved here, once per engine build; cached plans of a previous engine go
-            def branch(prefix, bcfg, provider):
+            def branch(prefix, bcfg, provider, crops):
                 if bcfg.type == 'ZoeDepth':
                     return ExternalCoreBranchNet(sd, prefix, bcfg, self.patch_process_shape, dt, dev, provider)
-                return BranchNet(sd, prefix, bcfg, self.patch_process_shape, dt, dev)
+                return BranchNet(sd, prefix, bcfg, self.patch_process_shape, dt, dev, ops=self.ops, crops=crops)
             self._engine = dict(
-                coarse=branch("coarse_branch.", cfg.coarse_branch, self.core_providers[0]),
-                fine=branch("fine_branch.", cfg.fine_branch, self.core_providers[1]),
+                coarse=branch("coarse_branch.", cfg.coarse_branch, self.core_providers[0], False),
+                fine=branch("fine_branch.", cfg.fine_branch, self.core_providers[1], True),
                 g2l=G2LNet(sd, cfg.guided_fusion, dt, dev),
                 fusion=FusionNet(sd, cfg, dt, dev))
             self._device = dev

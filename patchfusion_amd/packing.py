@@ -36,6 +36,8 @@ class PackedConv:
     wino_up: Optional[torch.Tensor] = None  # m = 4 only: the same filters in the fragment order of the fused kernel (winograd_filters_fused)
     wino_u3: Optional[torch.Tensor] = None  # m = 4 only: wino_u as the three bf16 planes of the split-precision GEMM, chunk-major [3, 36, Kpad1/32, rows, 32]
     w3: Optional[torch.Tensor] = None       # float32 1x1 layers with cin % 32 == 0: the weight's three bf16 planes, chunk-major [3, cin/32, rows, 32] (csrc/conv1x1_split3.hip)
+    col_exp: Optional[torch.Tensor] = None  # fp16x2 linears (pack_conv_f16x2): int32 column exponents f_n [rows]
+    in_exp: Optional[torch.Tensor] = None   # fp16x2 linears: int32 input-channel exponents e_k [cin] (the producer writes x / 2^e_k)
 
     def to(self, device):
         self.w = self.w.to(device)
@@ -47,6 +49,10 @@ class PackedConv:
             self.wino_u3 = self.wino_u3.to(device)
         if self.w3 is not None:
             self.w3 = self.w3.to(device)
+        if self.col_exp is not None:
+            self.col_exp = self.col_exp.to(device)
+        if self.in_exp is not None:
+            self.in_exp = self.in_exp.to(device)
         if self.bias is not None:
             self.bias = self.bias.to(device)
         if self.scale is not None:
@@ -274,6 +280,76 @@ def pack_conv_split3(weight, bias=None, *, scale=None, kmajor=None):
         sp = torch.zeros(rows)
         sp[:cout] = scale.detach().float().cpu()
     return PackedConv(planes, bp, sp, 1, 1, cin, cout_store, cout)
+
+
+# ---- fp16x2 linears (csrc/gemm_split3.hip pf_gemm_f16x2) --------------------------------------------------------------------------------------
+# Each float32 operand is two fp16 planes with a power-of-two scale along K:  x[k] = 2^e_k (h + l),  W[n][k] 2^e_k = 2^f_n (h' + l').  The scales are
+# STATIC: every K-side operand of a ViT block linear has a bound that the weights fix (no runtime range pass), and e_k is the smallest integer with
+# bound_k / 2^e_k <= 2^14 (one bit of headroom below 2^15 for the float32 rounding of the value itself; fp16 holds 65504).  Bounds in float64,
+# exponents on integers.
+
+def layernorm_bound(gamma, beta):
+    """|LayerNorm(x)[k]| <= |gamma_k| sqrt(D - 1) + |beta_k|: a normalised row has zero mean and sum of squares <= D, so one entry is at most
+    sqrt(D - 1) in magnitude (eps only shrinks it)"""
+    g, b = gamma.detach().double().cpu(), beta.detach().double().cpu()
+    return g.abs() * math.sqrt(g.numel() - 1) + b.abs()
+
+
+def gelu_linear_bound(weight, bias, in_bound):
+    """|GELU(W x + b)[n]| for |x_k| <= in_bound_k: |z_n| <= sum_k |W[n,k]| in_bound_k + |b_n|, GELU(z) <= z for z >= 0 and |GELU(z)| < 0.17 for z < 0"""
+    w = weight.detach().double().cpu()
+    z = w.abs() @ in_bound.double()
+    if bias is not None:
+        z = z + bias.detach().double().cpu().abs()
+    return torch.clamp(z, min=0.17)
+
+
+def _clog2(a):
+    """ceil(log2 a) of a finite a > 0 (exact: frexp)"""
+    f, e = math.frexp(a)
+    return e - 1 if f == 0.5 else e
+
+
+def bound_exponents(bound):
+    """e_k = ceil(log2 bound_k) - 14 (bound_k / 2^e_k <= 2^14); 0 for a zero bound"""
+    return torch.tensor([_clog2(float(b)) - 14 if b > 0 else 0 for b in bound.double().tolist()], dtype=torch.int32)
+
+
+def split_f16x2(v):
+    """float32 tensor (|v| <= 2^15) -> two float16 tensors (h, l): h = fp16_rn(v), l = fp16_rn(v - h) (v - h is exact in float32)"""
+    v = v.float()
+    h = v.half()
+    return h, (v - h.float()).half()
+
+
+def pack_conv_f16x2(weight, bias=None, scale=None, in_bound=None):
+    """nn.Linear weight [Cout, Cin] for the fp16x2 GEMM (pf_gemm_f16x2), given the static bound of its input channels (float64 [Cin]).
+    PackedConv with w = two chunk-major fp16 planes [2, Cin/32, rows, 32] of W[n][k] 2^(e_k - f_n), col_exp = f_n int32 [rows] (f_n = max_k of
+    ceil(log2 |W[n,k]|) + e_k, minus 15: every entry of the planes' sum is <= 2^15), in_exp = e_k int32 [Cin] for the producer; bias / scale float32."""
+    w = weight.detach().float().cpu()
+    cout, cin = w.shape
+    assert cin % 32 == 0, "fp16x2 GEMM: K must be a multiple of 32"
+    assert in_bound is not None and in_bound.numel() == cin
+    cout_store = round_up(cout, 4)
+    rows = round_up(cout_store, 16)
+    e = bound_exponents(in_bound)
+    wp = torch.zeros(rows, cin)
+    wp[:cout] = w
+    mant, ex = torch.frexp(wp.double().abs())                      # |w| = mant 2^ex, mant in [0.5, 1)
+    cl = torch.where(mant == 0.5, ex - 1, ex).long() + e.long()[None, :]
+    cl = torch.where(wp != 0, cl, torch.full_like(cl, -(1 << 30)))
+    f = cl.max(dim=1).values
+    f = torch.where(f > -(1 << 30), f - 15, torch.zeros_like(f))
+    v = torch.ldexp(wp.double(), (e.long()[None, :] - f[:, None]).double())
+    planes = rows_to_kmajor(torch.stack(split_f16x2(v.float())).contiguous())
+    bp = sp = None
+    if bias is not None:
+        bp = torch.zeros(rows)
+        bp[:cout] = bias.detach().float().cpu()
+    if scale is not None:
+        sp = torch.zeros(rows)
+        sp[:cout] = scale.detach().float().cpu()
+    return PackedConv(planes, bp, sp, 1, 1, cin, cout_store, cout, col_exp=f.to(torch.int32), in_exp=e)
 
 
 def pack_conv_transpose(weight, bias, *, dtype):
