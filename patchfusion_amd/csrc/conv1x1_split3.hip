@@ -288,7 +288,9 @@ extern "C" int pf_conv1x1_split3(const pf_conv_params* p, const void* w3, int w3
   if ((p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) return PF_ERR_ARG;
   const long M = (long)p->B * p->OH * p->OW;
   if (M <= 0 || M >= (1L << 31) || (long)w3_rows * 64 >= (1L << 31)) return PF_ERR_ARG;
-  if ((reinterpret_cast<size_t>(p->x) | reinterpret_cast<size_t>(p->y) | reinterpret_cast<size_t>(w3)) & 15) return PF_ERR_ARG;
+  // float4 loads / stores: x, y and w3 through the loaders and the store, bias and scale in registers, res and res2 in the epilogue
+  if ((reinterpret_cast<size_t>(p->x) | reinterpret_cast<size_t>(p->y) | reinterpret_cast<size_t>(w3) | reinterpret_cast<size_t>(p->res) |
+       reinterpret_cast<size_t>(p->res2) | reinterpret_cast<size_t>(p->bias) | reinterpret_cast<size_t>(p->scale)) & 15) return PF_ERR_ARG;
   // PF_C1_BM = 64 | 128 forces a token tile (A/B, tests); default 64 (two blocks per CU).  PF_C1_PERSIST=0: one tile per block (A/B, tests).
   static const int force = [] { const char* e = getenv("PF_C1_BM"); return e ? atoi(e) : 0; }();
   static const bool persist = [] { const char* e = getenv("PF_C1_PERSIST"); return !(e && e[0] == '0'); }();

@@ -274,6 +274,23 @@ const W3Switches& w3_switches() {
   return sw;
 }
 
+// With more than one window, window k's output is written before window k + 1's input (and its one-pixel halo across the seam) is read: x and y
+// must not share an element (a single window reads all of x first, like the unwindowed sequence).  Two channel slices of one NHWC buffer (equal
+// pixel strides, the engine's concat buffers) share none when y's channels [r, r + Cout) of a row, r = (y - x) mod ld in floats, miss x's [0, Cin)
+// without wrapping into the next row; other layouts are refused whenever their byte spans overlap.
+bool windows_alias(const pf_conv_params* p) {
+  const char* xa = static_cast<const char*>(p->x);
+  const char* ya = static_cast<const char*>(p->y);
+  const long px = (long)p->B * p->H * p->W;
+  const long xb = (px - 1) * p->x_ld * 4 + (long)p->Cin * 4, yb = (px - 1) * p->y_ld * 4 + (long)p->Cout * 4;
+  if (!(xa < ya + yb && ya < xa + xb)) return false;
+  const long d = (long)(ya - xa);
+  if (p->x_ld != p->y_ld || p->x_ld <= 0 || d % 4) return true;
+  long r = (d / 4) % p->x_ld;
+  if (r < 0) r += p->x_ld;
+  return !(r >= p->Cin && r + p->Cout <= p->x_ld);
+}
+
 // F(4x4,3x3) with the transform-domain GEMM in split precision: V is written as three bf16 planes, U3 = the three planes of G g G^T
 // (chunk-major [3][36][Cin/32][u_rows][32] bf16 = PackedConv.wino_u3, the split3 of packing.winograd_filters), ONE batched pf_gemm_split3 launch (plane = blockIdx.y), M float32.
 int run_split3(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, void* V3, float* M, long window, hipStream_t st) {
@@ -289,14 +306,8 @@ int run_split3(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, 
   const W3Switches& sw = w3_switches();
   const int tgrid = sw.tgrid, cap = sw.cap;
   hipEvent_t tok = sw.token ? gemm_token() : nullptr;
-  // With more than one window, window k's output is written before window k + 1's input (and its one-pixel halo across the seam) is read: x and y must
-  // not overlap (a single window reads all of x first, like the unwindowed sequence).  Refused instead of computing from half-overwritten input.
-  if (window < Tall) {
-    const char* xa = static_cast<const char*>(p->x);
-    const char* ya = static_cast<const char*>(p->y);
-    const long xb = ((long)p->B * p->H * p->W - 1) * p->x_ld * 4 + (long)p->Cin * 4, yb = ((long)p->B * p->H * p->W - 1) * p->y_ld * 4 + (long)p->Cout * 4;
-    if (xa < ya + yb && ya < xa + xb) return PF_ERR_ARG;
-  }
+  // (x and y of a layer in several windows must not share an element: windows_alias.)  Refused instead of computing from half-overwritten input.
+  if (window < Tall && windows_alias(p)) return PF_ERR_ARG;
   // TILE WINDOWS (round 5): the layer's tiles go through the three steps `window` tiles at a time, all windows through the SAME V / M arena -- launches
   // of one stream are ordered.  Winograd tiles are independent, so the numbers do not depend on the window.
   for (long t0 = 0; t0 < Tall; t0 += window) {
@@ -364,12 +375,7 @@ int run_f16x2(const pf_conv_params* p, const float* U, int u_rows, void* V2, flo
   const long Tall = (long)p->B * TH * TW;
   if (Tall > 0x7fffffffL) return PF_ERR_ARG;
   if (window <= 0 || window > Tall) window = Tall;
-  if (window < Tall) {                                  // (the alias rule of run_split3)
-    const char* xa = static_cast<const char*>(p->x);
-    const char* ya = static_cast<const char*>(p->y);
-    const long xb = ((long)p->B * p->H * p->W - 1) * p->x_ld * 4 + (long)p->Cin * 4, yb = ((long)p->B * p->H * p->W - 1) * p->y_ld * 4 + (long)p->Cout * 4;
-    if (xa < ya + yb && ya < xa + xb) return PF_ERR_ARG;
-  }
+  if (window < Tall && windows_alias(p)) return PF_ERR_ARG;   // (the alias rule of run_split3)
   const F16x2Scratch sc = f16x2_scratch(scratch, p->Cin, u_rows);
   const float* x = static_cast<const float*>(p->x);
   if (hipMemsetAsync(sc.cmax, 0, (size_t)p->Cin * 4, st) != hipSuccess) return PF_ERR_LAUNCH;

@@ -112,6 +112,20 @@ def _conv1x1_split3_wanted(M, pw):
     return tiles >= 512 and pw.cout >= 64
 
 
+def conv1x1_split3_layout_ok(pw, x_ptr, x_ld, y_ptr, y_ld, res_ptr=None, res_ld=0, res2_ptr=None, res2_ld=0):
+    """the layout rule of csrc/conv1x1_split3.hip (pf_conv1x1_split3), on pointer values and pixel strides in floats: float4 loads and stores need
+    x, y, res, res2 (and the packed bias / scale) on 16-byte boundaries and every ld a multiple of 4; x_ld >= Cin, Cin % 32 == 0, Cout % 4 == 0"""
+    if pw.w3 is None or pw.cin % 32 or pw.cout % 4 or x_ld < pw.cin or y_ld < pw.cout:
+        return False
+    ptrs = [x_ptr, y_ptr, pw.w3.data_ptr()] + [t.data_ptr() for t in (pw.bias, pw.scale) if t is not None]
+    lds = [x_ld, y_ld]
+    for ptr, ld in ((res_ptr, res_ld), (res2_ptr, res2_ld)):
+        if ptr is not None:
+            ptrs.append(ptr)
+            lds.append(ld)
+    return all(v % 16 == 0 for v in ptrs) and all(v % 4 == 0 for v in lds)
+
+
 def _split3_three_step(pw):
     """does the three-step form of this layer run its GEMM in split precision? (filters packed as three planes and PF_WINO_SPLIT3 != 0)"""
     return pw.wino_u3 is not None and _env("PF_WINO_SPLIT3", "1") != "0"
@@ -219,6 +233,11 @@ def wino3_window(B, H, W, pw):
     return window, nwin, (36 * window * pw.cin * 3 + 1) // 2, 36 * window * pw.cout
 
 
+def _align16(*ts):
+    """the 16-byte alignment of each tensor's data pointer: part of the plan key, because the route may depend on it (conv1x1_split3_layout_ok)"""
+    return tuple(None if t is None else t.data_ptr() % 16 for t in ts)
+
+
 class HipOps:
     name = "hip"
 
@@ -268,7 +287,7 @@ class HipOps:
             # bf16 linear layers with many token rows (ViT blocks, DPT projections): 256 x 128 ping-pong tiles (csrc/gemm_split3.hip, PLAIN)
             return "pp", p, None
         if (pw.w3 is not None and x4.dtype == torch.float32 and f32_io and stride == 1 and pad == 0 and s == 1 and not direct and
-                _conv1x1_split3_wanted(B * H * W, pw)):
+                conv1x1_split3_layout_ok(pw, p.x, p.x_ld, p.y, p.y_ld, p.res, p.res_ld, p.res2, p.res2_ld) and _conv1x1_split3_wanted(B * H * W, pw)):
             # float32 1x1 layers with enough tokens: split-precision product on the bf16 matrix cores, x split in the kernel's loader
             return "s3_1x1", p, (_p(pw.w3), pw.w3.shape[2])
         wino = winograd_applies(pw, B * H * W, stride, pad, act) and not direct
@@ -324,7 +343,8 @@ class HipOps:
         refreshes the four data pointers (round-3 review: 22 us of Python per library call, most of it here)."""
         if _timed is None and _direct is None:
             key = (id(pw), x.shape, x.stride(), y.shape, y.stride(), stride, pad, act, relu_in, x.dtype, y.dtype, x.device,
-                   None if res is None else (res.shape, res.stride(), res.dtype), None if res2 is None else (res2.shape, res2.stride(), res2.dtype))
+                   None if res is None else (res.shape, res.stride(), res.dtype), None if res2 is None else (res2.shape, res2.stride(), res2.dtype),
+                   _align16(x, y, res, res2))
             ent = _CONV_CACHE.get(key)
             if ent is None or ent[0] is not pw:
                 if len(_CONV_CACHE) > 4096:

@@ -40,7 +40,9 @@ TILES = tuple(range(16)) if os.environ.get("PF_HEADLINE_ALL", "0") == "1" else (
 SAMPLES = 4096
 TOL = {"fp32": dict(max=2e-5, p99=1e-5, mean=2e-6), "bf16": dict(max=5e-3, p99=2e-3, mean=6e-4)}
 TOL["fp32_mfma_only"] = TOL["fp32"]
-F32_MFMA_ONLY_ENV = {"PF_LINEAR_SPLIT3": "0", "PF_WINO_SPLIT3": "0"}          # every GEMM on the f32 MFMA (bench.py `f32_mfma_only`)
+# every GEMM on the f32 MFMA (bench.py `f32_mfma_only`; without PF_CONV1X1_SPLIT3=0 the 1x1 layers would still take the split route s3_1x1)
+F32_MFMA_ONLY_ENV = {"PF_LINEAR_SPLIT3": "0", "PF_WINO_SPLIT3": "0", "PF_CONV1X1_SPLIT3": "0"}
+F32_ROUTES = {"direct", "fused", "wino"}             # HipOps._conv_plan's routes on the float32 MFMA / FMA units
 FEATURE_REL_RMS = 1e-5
 # the coarse branch's own depth is an INTERMEDIATE (it enters the fusion net as one of 5 input channels); with the synthetic
 # weights its bin softmax is far more selective than the fusion head's (depths 0.56..0.99, std 0.039), so isolated pixels
@@ -147,14 +149,32 @@ def _stats(diff):
 def test_configs2_vitl_4k_p16_matches_oracle(oracle_sample, variant):
     cfg, sd, img, ref_coarse, ref_tiles, _ = oracle_sample
     dtype = "bf16" if variant == "bf16" else "fp32"
+    from patchfusion_amd import hip_ops
+    routes, saved = set(), {k: hip_ops.HipOps.__dict__[k] for k in ("_conv_exec", "conv_split3", "conv_f16x2")}
+
+    def record(name, fn):
+        def wrapped(*a, **k):
+            routes.add(a[0] if name == "_conv_exec" else name)
+            return fn(*a, **k)
+        return staticmethod(wrapped)
     with _env(F32_MFMA_ONLY_ENV if variant == "fp32_mfma_only" else {}):
-        m = PatchFusion(cfg, compute_dtype=dtype).eval()
-        m.load_state_dict(sd, strict=True)
-        m = m.cuda()
-        lr = m.resizer(img)
-        with torch.no_grad():
-            d, _ = m(mode="infer", image_lr=lr, image_hr=img, cai_mode="m1", process_num=8)
-        torch.cuda.synchronize()
+        hip_ops.refresh_env()
+        for k, v in saved.items():
+            setattr(hip_ops.HipOps, k, record(k, v.__func__))
+        try:
+            m = PatchFusion(cfg, compute_dtype=dtype).eval()
+            m.load_state_dict(sd, strict=True)
+            m = m.cuda()
+            lr = m.resizer(img)
+            with torch.no_grad():
+                d, _ = m(mode="infer", image_lr=lr, image_hr=img, cai_mode="m1", process_num=8)
+            torch.cuda.synchronize()
+        finally:
+            for k, v in saved.items():
+                setattr(hip_ops.HipOps, k, v)
+    hip_ops.refresh_env()
+    if variant == "fp32_mfma_only":
+        assert routes and routes <= F32_ROUTES, f"a split-precision route ran in the f32-MFMA-only variant: {sorted(routes - F32_ROUTES)}"
     assert tuple(d.shape) == (1, 1, 4 * 392, 4 * 518)
     got = torch.stack([d[0, 0, (t // 4) * 392:(t // 4 + 1) * 392, (t % 4) * 518:(t % 4 + 1) * 518] for t in TILES])
     st_tiles = _stats((got - ref_tiles).abs())
