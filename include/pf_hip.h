@@ -175,6 +175,13 @@ int pf_vit_attention_split3(const void* qkv3, long plane_in, void* out3, long pl
  * row offsets inside one image).  Replaces dinov2/layers/attention.py:53-60. */
 int pf_vit_attention_split3_v2(const void* qkv3, long plane_in, void* out3, long plane_out, int kmajor, int B, int S, int Hh, int queries_per_wave,
                                int schedule, void* stream);
+/* BEiT attention with a per-head relative-position bias (the MiDaS DPT_BEiT_L_384 core that midas.py:189-316 wraps, loaded at midas.py:340;
+ * MiDaS v3.1 backbones/beit.py attention_forward + _get_rel_pos_bias): softmax(q k^T / 8 + bias[h, idx(i, j)]) v, operands as
+ * pf_vit_attention_split3_v2 (the two-phase kernel, same MFMA arithmetic).  S = th * tw + 1 (cls first); tab [Hh][(2 th - 1)(2 tw - 1) + 3]
+ * float32, the bias table already interpolated to the (th, tw) window AND multiplied by log2(e); idx: patch x patch (yi - yj + th - 1)(2 tw - 1)
+ * + (xi - xj + tw - 1), cls row -> entry n - 3, cls column -> n - 2, cls x cls -> n - 1.  queries_per_wave 16, 32 or 0 (as v2).  S < 2^20. */
+int pf_vit_attention_split3_rpb(const void* qkv3, long plane_in, void* out3, long plane_out, int kmajor, int B, int S, int Hh, const float* tab,
+                                int th, int tw, int queries_per_wave, void* stream);
 /* float32 [rows][x_ld] -> three bf16 planes [3][rows][y_ld], plane stride `plane` elements (the split producers fuse into their stores) */
 int pf_split3(const float* x, int x_ld, void* y, int y_ld, long plane, long rows, int cols, void* stream);
 
@@ -182,6 +189,13 @@ int pf_split3(const float* x, int x_ld, void* y, int y_ld, long plane, long rows
 /* (x - mean)/std + 14x14/14 patch gather: NCHW float image -> im2col rows [B*th*tw][ld] (K order
  * ky,kx,c).  Replaces depth_anything.py:184-190 (Normalize) + the unfold implied by patch_embed.py:76 */
 int pf_patch_im2col(const float* img, int B, int H, int W, void* out, int ld, int dtype, void* stream);
+/* (x - mean[c])/std[c] + patch x patch / patch gather: NCHW float image -> float32 im2col rows [B*(H/patch)*(W/patch)][ld] (K order ky,kx,c;
+ * columns 3 patch^2 .. ld-1 zero).  Replaces midas.py:160-169 (PrepForMidas Normalize(0.5, 0.5)) + the unfold implied by the BEiT patch_embed.proj
+ * 16x16/16 conv of the core loaded at midas.py:340.  pf_patch_im2col (14x14, ImageNet statistics) is unchanged. */
+int pf_patch_im2col_norm(const float* img, int B, int H, int W, int patch, const float* mean3, const float* std3, float* out, int ld, void* stream);
+/* readout 'project' operand rows (MiDaS utils ProjectReadout, the act_postprocess*.0 of the core loaded at midas.py:340): x [B*S][x_ld] float32
+ * token rows (cls first) -> y[b*(S-1) + t] = [x[b*S + 1 + t][0:D] | x[b*S][0:D]] (y_ld >= 2 D).  D, x_ld, y_ld multiples of 4; 16-byte pointers. */
+int pf_readout_concat(const float* x, int x_ld, int B, int S, int D, float* y, int y_ld, void* stream);
 /* tokens[b,0,:] = cls + pos[0]; tokens[b,1+t,:] = emb[b*(S-1)+t,:] + pos[1+t]  (vision_transformer.py:222-223) */
 int pf_assemble_tokens(const void* emb, void* tokens, const float* cls, const float* pos, int B, int S, int D, int dtype,
                        void* stream);

@@ -72,6 +72,9 @@ SIGNATURES = {
     "pf_vit_attention_qkv_split3": [vp, vp, cl, ci, ci, ci, ci, vp],
     "pf_vit_attention_split3": [vp, cl, vp, cl, ci, ci, ci, ci, vp],
     "pf_vit_attention_split3_v2": [vp, cl, vp, cl, ci, ci, ci, ci, ci, ci, vp],
+    "pf_vit_attention_split3_rpb": [vp, cl, vp, cl, ci, ci, ci, ci, vp, ci, ci, ci, vp],
+    "pf_patch_im2col_norm": [vp, ci, ci, ci, ci, vp, vp, vp, ci, vp],
+    "pf_readout_concat": [vp, ci, ci, ci, ci, vp, ci, vp],
     "pf_conv_winograd_fused": [C.POINTER(ConvParams), vp, ci, ci, vp],
     "pf_conv_winograd_fused_timed": [C.POINTER(ConvParams), vp, ci, ci, ci, C.POINTER(cf), vp],
     "pf_attractor": [vp, ci, ci, ci, cf, ci, ci, vp, ci, ci, vp, ci, ci, ci, ci, vp],

@@ -37,6 +37,11 @@ class BaselinePretrain(PatchFusion):
                 raise NotImplementedError(self.branch_cfg.midas_model_type)
         elif self.branch_cfg.type != 'ZoeDepth':
             raise NotImplementedError
+        if isinstance(core_provider, str):         # core_provider="native": midas_core.MidasBeitCore from the branch's midas_model_type
+            if core_provider != "native" or self.branch_cfg.type != 'ZoeDepth':
+                raise ValueError(f"core_provider={core_provider!r}: only 'native' for a type-'ZoeDepth' branch")
+            from .midas_core import native_providers
+            core_provider = native_providers({"coarse_branch": self.branch_cfg, "fine_branch": {}})[0]
         self.core_provider = core_provider
         self.prefix = f"{target}_branch."
         self.resizer = Resizer(self.patch_process_shape[1], self.patch_process_shape[0], 32 if self.branch_cfg.type == 'ZoeDepth' else 14)

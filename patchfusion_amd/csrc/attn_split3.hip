@@ -59,9 +59,19 @@ __device__ __forceinline__ bf16x8 tr_pair(const char* p0, const char* p1) {
 
 constexpr int KS_BYTES = 3 * 64 * 128;          // one K (or V) tile: three planes x 64 keys x 128 bytes = 24 KiB = 24 DMA pieces
 
-template <int QG>
-__global__ __launch_bounds__(256, 2) void vit_attention_split3_v2_kernel(const bf16_t* __restrict__ qkv3, long plane_in, bf16_t* __restrict__ out3,
-                                                                         long plane_out, int S, int Hh, float qscale, long kmaj_rows, int n_qb, int dbg) {
+// Per-head relative-position bias (RPB = true; BEiT, MiDaS v3.1 backbones/beit.py attention_forward / _get_rel_pos_bias): the logits become
+// s * qscale + tab[h][idx(i, j)], tab pre-multiplied by log2(e) at pack time (base-2 softmax), idx as generate_relative_position_index:
+// patch x patch (yi - yj + th - 1)(2 tw - 1) + (xi - xj + tw - 1), cls row / cls column / cls x cls the last three entries.  The block stages the
+// rows of its head's table that its queries can reach (query rows y_lo .. y_hi -> dy in [y_lo, y_hi + th - 1], plus the three cls entries) in
+// LDS behind the K / V stages and gathers from there.  RPB = false is the unchanged kernel (vit_attention_split3_v2_kernel below).
+struct RpbArgs {
+  const float* tab;   // [Hh][ntab], ntab = (2 th - 1)(2 tw - 1) + 3
+  int th, tw;
+};
+
+template <int QG, bool RPB>
+__device__ __forceinline__ void attn_v2_body(const bf16_t* __restrict__ qkv3, long plane_in, bf16_t* __restrict__ out3, long plane_out, int S,
+                                             int Hh, float qscale, long kmaj_rows, int n_qb, int dbg, RpbArgs rpb) {
 #ifdef PF_ATTN_DBG   // timing decomposition (results wrong by construction; make attndbg, tools/attn_split3_time.py): PF_ATTN_DBG bit 0 = no DMA inside the tile
 #define ADBG(bit) (dbg & (bit))   // loop, 1 = no softmax VALU work, 2 = no QK MFMAs, 3 = no PV reads / MFMAs, 4 = no barriers
 #else
@@ -107,6 +117,28 @@ __global__ __launch_bounds__(256, 2) void vit_attention_split3_v2_kernel(const b
       }
     }
   };
+
+  // RPB: this block's slice of the table -> LDS (before the first DMA: the table loads' vmcnt wait then waits for nothing else)
+  const float* rtab = reinterpret_cast<const float*>(smem + 3 * KS_BYTES);
+  int qbase[QG], cls_at = 0;
+  float inv_tw = 0.f;
+  if constexpr (RPB) {
+    const int th = rpb.th, tw = rpb.tw, wq = 2 * tw - 1, ntab = (2 * th - 1) * wq + 3;
+    const int y_lo = (max(qb * QB, 1) - 1) / tw, y_hi = (max(min(qb * QB + QB, S) - 1, 1) - 1) / tw;
+    const int nsub = (y_hi - y_lo + th) * wq;
+    const float* src = rpb.tab + (long)h * ntab;
+    float* dst = reinterpret_cast<float*>(smem + 3 * KS_BYTES);
+    for (int i = tid; i < nsub; i += 256) dst[i] = src[y_lo * wq + i];
+    if (tid < 3) dst[nsub + tid] = src[ntab - 3 + tid];
+    cls_at = nsub;
+    inv_tw = 1.0f / (float)tw;
+#pragma unroll
+    for (int qg = 0; qg < QG; ++qg) {
+      const int qi = min(q0 + 16 * qg + r, S - 1);
+      const int pi = max(qi - 1, 0), yi = pi / tw, xi = pi - yi * tw;
+      qbase[qg] = qi == 0 ? -1 : (yi - y_lo + th - 1) * wq + xi + tw - 1;       // -1: the cls query
+    }
+  }
 
   issue(0, 1, ks_lds);
   issue(0, 2, vs_lds);
@@ -211,13 +243,21 @@ __global__ __launch_bounds__(256, 2) void vit_attention_split3_v2_kernel(const b
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             float v = sacc[qg][kf][e];             // raw q.k: the positive scale commutes with the max and is folded into the exponent's FMA below
+            if constexpr (RPB) {                   // (with a bias it does not: scaled + biased base-2 logits)
+              const int j = min(kt * 64 + 16 * kf + 4 * g + e, S - 1), p = j - 1;
+              const int yj = __float2int_rz(((float)p + 0.5f) * inv_tw);          // exact for p < 2^20 (host check)
+              int li = qbase[qg] - (yj * (rpb.tw - 1) + p);
+              li = j == 0 ? cls_at + 1 : li;
+              li = qbase[qg] < 0 ? (j == 0 ? cls_at + 2 : cls_at) : li;
+              v = fmaf(v, qscale, rtab[li]);
+            }
             if (LAST && 16 * kf + 4 * g + e >= rem) v = -INFINITY;
             sacc[qg][kf][e] = v;
             mx = fmaxf(mx, v);
           }
         mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run[qg], mx * qscale);
+        const float m_new = fmaxf(m_run[qg], RPB ? mx : mx * qscale);
         alpha[qg] = __builtin_amdgcn_exp2f(m_run[qg] - m_new);
         m_run[qg] = m_new;
         float psum = 0.f;
@@ -226,7 +266,8 @@ __global__ __launch_bounds__(256, 2) void vit_attention_split3_v2_kernel(const b
           float pv[8];
 #pragma unroll
           for (int t = 0; t < 8; ++t) {
-            pv[t] = __builtin_amdgcn_exp2f(fmaf(sacc[qg][2 * kk + (t >> 2)][t & 3], qscale, -m_new));
+            pv[t] = RPB ? __builtin_amdgcn_exp2f(sacc[qg][2 * kk + (t >> 2)][t & 3] - m_new)
+                        : __builtin_amdgcn_exp2f(fmaf(sacc[qg][2 * kk + (t >> 2)][t & 3], qscale, -m_new));
             psum += pv[t];
           }
           uint32_t hw[4], mw[4], lw[4];
@@ -289,6 +330,18 @@ __global__ __launch_bounds__(256, 2) void vit_attention_split3_v2_kernel(const b
   }
 }
 
+template <int QG>
+__global__ __launch_bounds__(256, 2) void vit_attention_split3_v2_kernel(const bf16_t* __restrict__ qkv3, long plane_in, bf16_t* __restrict__ out3,
+                                                                         long plane_out, int S, int Hh, float qscale, long kmaj_rows, int n_qb, int dbg) {
+  attn_v2_body<QG, false>(qkv3, plane_in, out3, plane_out, S, Hh, qscale, kmaj_rows, n_qb, dbg, RpbArgs{nullptr, 0, 0});
+}
+
+template <int QG>
+__global__ __launch_bounds__(256, 2) void vit_attention_split3_rpb_kernel(const bf16_t* __restrict__ qkv3, long plane_in, bf16_t* __restrict__ out3,
+                                                                          long plane_out, int S, int Hh, float qscale, long kmaj_rows, int n_qb,
+                                                                          const float* __restrict__ tab, int th, int tw) {
+  attn_v2_body<QG, true>(qkv3, plane_in, out3, plane_out, S, Hh, qscale, kmaj_rows, n_qb, 0, RpbArgs{tab, th, tw});
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // The PIPELINED kernel (round 6, the default).  Two measurements shaped it (profiles/r6_attention_v2.md, profiles/r6_issue_probe.md):
@@ -818,6 +871,44 @@ extern "C" int pf_vit_attention_split3_v2(const void* qkv3, long plane_in, void*
                        B * Hh, dbg);
   }
 #undef ATTN_LAUNCH
+  return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
+}
+
+// C entry: see include/pf_hip.h.  The two-phase kernel with the relative-position bias (RPB = true above).
+extern "C" int pf_vit_attention_split3_rpb(const void* qkv3, long plane_in, void* out3, long plane_out, int kmajor, int B, int S, int Hh,
+                                           const float* tab, int th, int tw, int queries_per_wave, void* stream) {
+  if (!qkv3 || !out3 || !tab || B <= 0 || Hh <= 0 || th <= 0 || tw <= 0 || plane_in < (long)B * S * Hh * 192 || plane_out < (long)B * S * Hh * 64)
+    return PF_ERR_ARG;
+  if ((long)th * tw + 1 != S || S >= (1 << 20)) return PF_ERR_ARG;               // one cls token + the th x tw grid; the key-row division is exact below 2^20
+  if ((long)S * Hh * 192 * 2 >= (1L << 31)) return PF_ERR_ARG;
+  if (queries_per_wave != 0 && queries_per_wave != 16 && queries_per_wave != 32) return PF_ERR_ARG;
+  int qw = queries_per_wave;
+  if (qw == 0) qw = (long)((S + 127) / 128) * B * Hh >= 512 ? 32 : 16;
+  const int QB = 4 * qw, n_qb = (S + QB - 1) / QB, wq = 2 * tw - 1;
+  int rows = 0;                                                                  // the largest table slice a block stages (see attn_v2_body)
+  for (int qb = 0; qb < n_qb; ++qb) {
+    const int y_lo = ((qb * QB > 1 ? qb * QB : 1) - 1) / tw, last = (qb * QB + QB < S ? qb * QB + QB : S) - 1;
+    const int y_hi = ((last > 1 ? last : 1) - 1) / tw;
+    rows = rows > y_hi - y_lo + th ? rows : y_hi - y_lo + th;
+  }
+  const int lds = 3 * KS_BYTES + ((rows * wq + 3) * 4 + 15) / 16 * 16;
+  if (lds > 160 * 1024) return PF_ERR_ARG;
+  const void* k = qw == 32 ? reinterpret_cast<const void*>(vit_attention_split3_rpb_kernel<2>) : reinterpret_cast<const void*>(vit_attention_split3_rpb_kernel<1>);
+  static int attr_lds[2] = {0, 0};
+  if (attr_lds[qw == 32] < lds) {
+    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return PF_ERR_LAUNCH;
+    attr_lds[qw == 32] = lds;
+  }
+  const float qscale = 0.125f * 1.4426950408889634f;        // head_dim^-1/2 times log2(e); the table is pre-multiplied by log2(e)
+  const long kmaj_rows = kmajor ? (long)B * S : 0L;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid(n_qb * B * Hh), block(256);
+  if (qw == 32)
+    hipLaunchKernelGGL(vit_attention_split3_rpb_kernel<2>, grid, block, lds, st, (const bf16_t*)qkv3, plane_in, (bf16_t*)out3, plane_out, S, Hh, qscale, kmaj_rows,
+                       n_qb, tab, th, tw);
+  else
+    hipLaunchKernelGGL(vit_attention_split3_rpb_kernel<1>, grid, block, lds, st, (const bf16_t*)qkv3, plane_in, (bf16_t*)out3, plane_out, S, Hh, qscale, kmaj_rows,
+                       n_qb, tab, th, tw);
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
 }
 

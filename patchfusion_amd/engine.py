@@ -405,6 +405,17 @@ class ExternalCoreBranchNet:
 
     def forward(self, ops, img, taps=None):
         dt, dev = self.dtype, self.device
+        if hasattr(self.provider, "forward_nhwc"):               # a native core (midas_core.MidasBeitCore): NHWC straight into the clb buffer
+            if dt != F32:
+                raise NotImplementedError("the native MiDaS core runs in float32 only (compute_dtype='fp32')")
+            B, _, H, W = img.shape
+            clb = self.head.new_clb_buffer(ops, B, H, W)
+            _, feats = self.provider.forward_nhwc(ops, img, out_conv=clb[..., :32], rel=clb[..., 32 + self.head.emb:])
+            btl, blocks = feats[0], feats[1:5]
+            x_d0 = ops.empty(btl.shape[:3] + (self.C,), dt, dev)
+            ops.conv(btl, self.conv2, x_d0)
+            depth = self.head.run(ops, x_d0, blocks, clb, taps)
+            return depth, [x_d0] + blocks + [clb[..., :32]]
         rel, feats = self.provider(img)
         assert len(feats) == 6, "provider must return [btlnck, x_block0..3, out_conv]"
         nhwc = [f.detach().to(dev).permute(0, 2, 3, 1).contiguous().to(dt) for f in feats]      # re-layout only

@@ -666,6 +666,48 @@ class HipOps:
         check(_L.pf_qkv_split(_p(qkv), B, S, heads, _p(q), _p(k), _p(vt), Sp, 0.125, _dt(qkv), _stream()), "pf_qkv_split")
         check(_L.pf_vit_attention(_p(q), _p(k), _p(vt), _p(out), B, S, Sp, heads, _dt(qkv), _stream()), "pf_vit_attention")
 
+    @staticmethod
+    def vit_attention_rpb(qkv, out, B, S, heads, tab, th, tw):
+        """BEiT attention with a per-head relative-position bias (MiDaS DPT_BEiT_L_384 core, csrc/attn_split3.hip pf_vit_attention_split3_rpb):
+        qkv bfloat16 [3, B*S, 3*D] planes of the QKV GEMM -> out bfloat16 [3, B*S, D] (or chunk-major [3, D/32, B*S, 32]) planes; tab float32
+        [heads, (2 th - 1)(2 tw - 1) + 3] on the device, interpolated to (th, tw) and multiplied by log2(e) (packing.beit_rel_pos_tables)."""
+        kmaj = int(out.dim() == 4)
+        D = heads * 64
+        if qkv.dtype != torch.bfloat16 or tuple(qkv.shape) != (3, B * S, 3 * D) or not qkv.is_contiguous():
+            raise ValueError(f"vit_attention_rpb: qkv must be contiguous bfloat16 [3, {B * S}, {3 * D}], got {qkv.dtype} {tuple(qkv.shape)}")
+        if out.dtype != torch.bfloat16 or tuple(out.shape) != ((3, D // 32, B * S, 32) if kmaj else (3, B * S, D)) or not out.is_contiguous():
+            raise ValueError(f"vit_attention_rpb: bad output planes {out.dtype} {tuple(out.shape)}")
+        if S != th * tw + 1:
+            raise ValueError(f"vit_attention_rpb: S = {S} is not th * tw + 1 = {th * tw + 1}")
+        ntab = (2 * th - 1) * (2 * tw - 1) + 3
+        if tab.dtype != torch.float32 or tuple(tab.shape) != (heads, ntab) or not tab.is_contiguous() or tab.device != qkv.device:
+            raise ValueError(f"vit_attention_rpb: tab must be contiguous float32 [{heads}, {ntab}] on {qkv.device}")
+        check(_L.pf_vit_attention_split3_rpb(_p(qkv), qkv.stride(0), _p(out), out.stride(0), kmaj, B, S, heads, _p(tab), th, tw,
+                                             int(_env("PF_ATTN_QW", "0")), _stream()), "pf_vit_attention_split3_rpb")
+
+    @staticmethod
+    def patch_im2col_norm(img, out, patch, mean, std):
+        """img float32 [B,3,H,W] -> out float32 [B*(H/patch)*(W/patch), ld >= 3 patch^2] rows of (x - mean[c]) / std[c] (K order ky, kx, c)"""
+        B, Ci, H, W = img.shape
+        if img.dtype != torch.float32 or not img.is_contiguous() or Ci != 3 or H % patch or W % patch:
+            raise ValueError(f"patch_im2col_norm: img must be contiguous float32 [B,3,H,W] with H, W multiples of {patch}")
+        if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B * (H // patch) * (W // patch) or out.shape[1] < 3 * patch * patch \
+                or out.stride(1) != 1:
+            raise ValueError(f"patch_im2col_norm: bad output {out.dtype} {tuple(out.shape)}")
+        m3, s3 = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+        check(_L.pf_patch_im2col_norm(_p(img), B, H, W, patch, C.cast(m3, C.c_void_p), C.cast(s3, C.c_void_p), _p(out), out.stride(0), _stream()),
+              "pf_patch_im2col_norm")
+
+    @staticmethod
+    def readout_concat(x, y, B, S):
+        """x float32 [B*S, D] token rows (row stride >= D) -> y float32 [B*(S-1), 2D] rows [token | cls of its image]"""
+        D = x.shape[1]
+        if x.dtype != torch.float32 or y.dtype != torch.float32 or x.shape[0] != B * S or x.stride(1) != 1 or y.stride(1) != 1:
+            raise ValueError("readout_concat: float32 row-major operands required")
+        if tuple(y.shape) != (B * (S - 1), 2 * D) or D % 4 or x.stride(0) % 4 or y.stride(0) % 4 or (x.data_ptr() | y.data_ptr()) & 15:
+            raise ValueError(f"readout_concat: bad shapes / strides / alignment x {tuple(x.shape)} y {tuple(y.shape)}")
+        check(_L.pf_readout_concat(_p(x), x.stride(0), B, S, D, _p(y), y.stride(0), _stream()), "pf_readout_concat")
+
     # ---------------- Swin / G2L ----------------
     @staticmethod
     def swin_ln_partition(x, xw, g, b, eps, shift):

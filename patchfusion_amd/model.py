@@ -144,6 +144,12 @@ class PatchFusion(nn.Module, PyTorchModelHubMixin):
         # patchfusion.py:82-87: ensure_multiple_of 32 for the MiDaS-core branch, 14 for Depth-Anything
         self.resizer = Resizer(self.patch_process_shape[1], self.patch_process_shape[0],
                                32 if config.coarse_branch.type == 'ZoeDepth' else 14)
+        # core_providers="native": one midas_core.MidasBeitCore per type-'ZoeDepth' branch, built from its midas_model_type (BEiT types only)
+        if isinstance(core_providers, str):
+            if core_providers != "native":
+                raise ValueError(f"core_providers: 'native' or a (coarse, fine) pair, not {core_providers!r}")
+            from .midas_core import native_providers
+            core_providers = native_providers(config)
         self.core_providers = tuple(core_providers) if core_providers is not None else (None, None)
         self.spec = patchfusion_spec(config)
         _build_param_tree(self, self.spec)

@@ -432,3 +432,21 @@ def vit_pos_embed(pos_embed, th, tw):
     assert grid.shape[-2] == th and grid.shape[-1] == tw
     grid = grid.permute(0, 2, 3, 1).reshape(-1, dim)
     return torch.cat([pos[0, :1], grid], dim=0).contiguous()           # [1 + th*tw, D]
+
+
+def beit_rel_pos_table(table, pretrain, th, tw):
+    """One BEiT layer's relative-position bias table for the relative-position attention (csrc/attn_split3.hip pf_vit_attention_split3_rpb):
+    [(2 pretrain - 1)^2 + 3, heads] -> float32 [heads, (2 th - 1)(2 tw - 1) + 3], interpolated ONCE at load exactly as MiDaS v3.1's
+    _get_rel_pos_bias does per forward (the same F.interpolate call, float32, align_corners=False, the reshape(1, old_width, old_height, -1)
+    of a square pretrain grid), then multiplied by log2(e) for the kernel's base-2 softmax."""
+    import math
+
+    import torch.nn.functional as F
+    t = table.detach().float().cpu()
+    old = 2 * pretrain - 1
+    assert t.dim() == 2 and t.shape[0] == old * old + 3, tuple(t.shape)
+    sub = t[:old * old].reshape(1, old, old, -1).permute(0, 3, 1, 2)
+    new = F.interpolate(sub, size=(2 * th - 1, 2 * tw - 1), mode="bilinear")
+    new = new.permute(0, 2, 3, 1).reshape((2 * th - 1) * (2 * tw - 1), -1)
+    full = torch.cat([new, t[old * old:]])
+    return (full * math.log2(math.e)).t().contiguous()
