@@ -103,7 +103,8 @@ int pf_gemm_f16x2_points(const pf_conv_params* p, const int* col_exp, int grid_c
  * The persistent 192 x 192 kernel sums the three products hh, hl, lh in float32, applies ldexp(acc, f_n) and then the pf_conv epilogue
  * (bias -> act -> scale -> res -> res2, all float32), and stores one of: float32 [M][y_ld] (out_f32); three bf16 planes, row-major [3][M][y_ld]
  * (y_bstride); or, with korder bit 16, two fp16 chunk-major planes [2][Cout/32][M][32] of y / 2^out_exp[n] (y_ld == Cout, Cout % 32 == 0,
- * p->out_exp required).  No batch. */
+ * p->out_exp required); or, with korder bit 32, two fp16 ROW-major planes [2][M][y_ld] (y_bstride) of y / 2^out_exp[n] (p->out_exp required):
+ * q / k / v for pf_vit_attention_f16x2, which reads token rows.  Bits 16 and 32 exclude each other.  No batch. */
 int pf_gemm_f16x2(const pf_conv_params* p, void* stream);
 
 /* FUSED Winograd F(4x4, 3x3) (csrc/wino_fused.hip): the same layers in ONE kernel -- the transformed input and the transform-domain
@@ -175,6 +176,15 @@ int pf_vit_attention_split3(const void* qkv3, long plane_in, void* out3, long pl
  * row offsets inside one image).  Replaces dinov2/layers/attention.py:53-60. */
 int pf_vit_attention_split3_v2(const void* qkv3, long plane_in, void* out3, long plane_out, int kmajor, int B, int S, int Hh, int queries_per_wave,
                                int schedule, void* stream);
+/* The same attention on TWO SCALED fp16 PLANES (three v_mfma_f32_32x32x16_f16 per product term instead of six bf16 ones; the pipelined kernel's
+ * schedule): qkv2 = two fp16 planes [2][B*S][3*Hh*64] (plane stride plane_in elements) holding q[c] / 2^eq[c], k[c] / 2^ek[c], v[d] / 2^ev[d] as h + l
+ * (pf_gemm_f16x2 with korder bit 32; packing.vit_attn_f16x2_scales), with eq[c] + ek[c] = qk_exp[h] for EVERY channel c of head h; qk_exp = int32
+ * [Hh] on the device, folded into the base-2 softmax scale.  out2 = two fp16 planes, chunk-major [2][Hh*2][B*S][32] (plane stride plane_out elements), holding out[d] / 2^ev[d]: the
+ * input of the projection as a pf_gemm_f16x2 layer whose in_exp is ev.  With v_exp3 != NULL (int32 [Hh*64] on the device, ev) the output is
+ * written as THREE bf16 planes of out itself, chunk-major [3][Hh*2][B*S][32] -- the input of the projection as a pf_gemm_split3 layer (korder bit 1).
+ * Float32 softmax and accumulation.  Requires S * Hh * 384 bytes < 2^31. */
+int pf_vit_attention_f16x2(const void* qkv2, long plane_in, const int* qk_exp, void* out, long plane_out, const int* v_exp3, int B, int S, int Hh,
+                           void* stream);
 /* BEiT attention with a per-head relative-position bias (the MiDaS DPT_BEiT_L_384 core that midas.py:189-316 wraps, loaded at midas.py:340;
  * MiDaS v3.1 backbones/beit.py attention_forward + _get_rel_pos_bias): softmax(q k^T / 8 + bias[h, idx(i, j)]) v, operands as
  * pf_vit_attention_split3_v2 (the two-phase kernel, same MFMA arithmetic).  S = th * tw + 1 (cls first); tab [Hh][(2 th - 1)(2 tw - 1) + 3]

@@ -72,6 +72,7 @@ SIGNATURES = {
     "pf_vit_attention_qkv_split3": [vp, vp, cl, ci, ci, ci, ci, vp],
     "pf_vit_attention_split3": [vp, cl, vp, cl, ci, ci, ci, ci, vp],
     "pf_vit_attention_split3_v2": [vp, cl, vp, cl, ci, ci, ci, ci, ci, ci, vp],
+    "pf_vit_attention_f16x2": [vp, cl, vp, vp, cl, vp, ci, ci, ci, vp],
     "pf_vit_attention_split3_rpb": [vp, cl, vp, cl, ci, ci, ci, ci, vp, ci, ci, ci, vp],
     "pf_patch_im2col_norm": [vp, ci, ci, ci, ci, vp, vp, vp, ci, vp],
     "pf_readout_concat": [vp, ci, ci, ci, ci, vp, ci, vp],

@@ -27,6 +27,7 @@
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
 
+#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
@@ -704,6 +705,7 @@ __global__ __launch_bounds__(256, 2) void vit_attention_split3_pipe_kernel(const
   // two slots the step read; then refill them
   auto turn = [&](int j, int ks, int vs) {
     TL_MARK(8);                                          // [8] the four super-groups
+    // (vit_attention_f16x2_pipe_kernel below runs the same protocol with vmcnt(4): keep the two in step)
     asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     TL_MARK(1);                                          // [1] landing wait + barrier
     issue(j + 4, 1, kr_lds + ks);
@@ -828,6 +830,415 @@ __global__ __launch_bounds__(256, 2) void vit_attention_split3_pipe_kernel(const
 #endif
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// The pipelined kernel on TWO SCALED fp16 PLANES (round 10, pf_vit_attention_f16x2): the schedule, ring protocol, LDS swizzles, fragment maps, tail-first
+// grid order and key-split tail blocks of vit_attention_split3_pipe_kernel above, with every product as the three terms hl, lh, hh (smallest first, as
+// csrc/gemm_split3.hip F16) on v_mfma_f32_32x32x16_f16 instead of six bf16 terms.  A super-group is six MFMA slots (three on the S chain, three on an
+// O chain) and a steady step 24 MFMAs where the bf16x3 kernel issues 48; the float32 softmax is the same and rides the same way.
+//   Operands: q / k / v = two fp16 planes [2][B*S][3 D] of y / 2^e_n (pf_gemm_f16x2, korder bit 32).  QK^T contracts over the head's 64 channels, so the
+//   exponent of every PRODUCT q_c k_c must be the same along them: eq[c] + ek[c] = qk_exp[h] for every channel c of head h (the packer is free to share
+//   it between the two operands channel by channel).  logit = (q^ . k^) 2^qk_exp[h] / 8: the kernel sees only qk_exp[h] and folds it into the exp2 scale
+//   with ldexp (exact).  v keeps per-column exponents and they never enter the kernel: an output
+//   channel is a convex combination of v rows, |out_d| <= bound(v_d), so the projection's input exponent of channel d IS v's (packing.vit_attn_f16x2_scales)
+//   and the planes written are sum_j p_j v^_jd / l itself.  (v_exp3 != nullptr: the output goes out as THREE bf16 planes of out_d = 2^ev[d] sum / l
+//   instead, for a projection that stays on bf16x3.)
+//   Probabilities: P^ = 2^(s - m_ref) is split in registers as h = fp16(P^), l = fp16(P^ - h).  The exponent reference sits PSHIFT = 12 binary orders below
+//   the row maximum it was taken from and moves when a block's maximum exceeds it by more than 15 (deferred rescale as above, THR 3 instead of 24):
+//   P^ <= 2^15 < 65504 always, and the row's largest P^ is >= 2^12.  h + l is exact to 22 bits while l is a normal fp16, i.e. for P^ >= 2^-3 (p >= 2^-15 of
+//   the row's reference); below that the split drops at most 2^-25 per key in units where the row's sum is >= 2^12: at most S 2^-37 = 2^-27 of the sum
+//   at S = 1037, an eighth of a float32 ulp of the largest possible output.  O and l carry the 2^12 alike; it cancels in O / l.
+//   K ring: 3 slots x [2 planes][32 keys][128 B] = 24 KiB, V ring the same: 48 KiB per block (two blocks per CU, as before).  A wave moves two pieces per
+//   operand and block; the step-end wait is vmcnt(4): the four pieces of the previous step -- DMA pieces counted against DMA pieces only.
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
+constexpr int HB_BYTES = 2 * 32 * 128;          // one K (or V) block: two planes x 32 keys x 128 bytes = 8 KiB = 8 DMA pieces
+constexpr int PIPE_H_LDS = 6 * HB_BYTES;
+constexpr float PSHIFT_H = 12.0f, RESCALE_H = 15.0f;
+
+__device__ __forceinline__ uint32_t cvt_pk_h(float lo, float hi) {       // two floats -> packed fp16 pair, round to nearest even (the compiler's own conversion)
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){lo, hi}, f16x2_t));
+}
+__device__ __forceinline__ f16x8 tr_pair_h(const char* p0, const char* p1) {
+  const v4s a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)p0);
+  const v4s b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)p1);
+  return __builtin_bit_cast(f16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+__global__ __launch_bounds__(256, 2) void vit_attention_f16x2_pipe_kernel(const uint16_t* __restrict__ qkv2, long plane_in, const int* __restrict__ qk_exp,
+                                                                          uint16_t* __restrict__ out2, long plane_out, const int* __restrict__ v_exp3, int S,
+                                                                          int Hh, float qscale0, long kmaj_rows, int n_qb, int BH) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* const Kr = smem;
+  char* const Vr = smem + 3 * HB_BYTES;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int c = lane & 31, hi = lane >> 5;
+  int bh, qb;                                            // block order: as vit_attention_split3_pipe_kernel
+  {
+    const int bid = (int)blockIdx.x;
+    const bool tail = (S & 127) != 0 && (BH & 7) == 0 && n_qb > 1;
+    if (tail) {
+      if (bid < BH) { bh = bid; qb = n_qb - 1; }
+      else {
+        const int l = bid - BH, idx = l >> 3, nf = n_qb - 1;
+        bh = (idx / nf) * 8 + (l & 7);
+        qb = idx % nf;
+      }
+    } else {
+      const int l = xcd_remap(bid, (int)gridDim.x);
+      bh = l / n_qb;
+      qb = l - bh * n_qb;
+    }
+  }
+  const int b = bh / Hh, h = bh - b * Hh;
+  const int NB = (S + 31) / 32;
+  const bool ksplit = S - qb * 128 <= 32 && NB >= 8;     // key-split tail blocks (see above)
+  const int q0 = qb * 128 + (ksplit ? 0 : wave * 32);
+  const bool has_q = q0 < S;
+  const int D = Hh * 64;
+  const long rs = 3L * D;
+  const uint16_t* base = qkv2 + (long)b * S * rs + h * 64;
+  const float qscale = ldexpf(qscale0, qk_exp[h]);       // 2^(eq + ek) log2(e) / 8: the head's exponents leave through the exp2 argument
+
+  // ---- DMA roles: wave w moves pieces 2 w, 2 w + 1 of a block (piece p = plane p >> 2, keys 8 (p & 3) .. + 7); lane L = row L >> 3, LDS chunk L & 7
+  const unsigned rs_b = (unsigned)(rs * 2);
+  const unsigned kchunk = (unsigned)(((lane & 7) ^ ((lane >> 4) & 3)) << 4);        // ^ 64 for the odd pieces: (key >> 1) & 7 = 4 (p & 1) + (L >> 4)
+  const unsigned vchunk = (unsigned)(((lane & 7) ^ (((lane >> 4) & 1) << 2)) << 4);
+  const unsigned kr_lds = lds_addr_of(Kr), vr_lds = lds_addr_of(Vr);
+  auto issue = [&](int jb, int which, unsigned lds_dst) {              // which = 1: K rows, 2: V rows of key block jb
+    const char* sb = reinterpret_cast<const char*>(base + which * D);
+    const unsigned chunk = which == 1 ? kchunk : vchunk;
+    if (jb * 32 + 32 <= S) {
+      const unsigned lane_off = (unsigned)(jb * 32 + (lane >> 3)) * rs_b;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int p = wave * 2 + i;
+        const unsigned ch = which == 1 ? chunk ^ (unsigned)((p & 1) << 6) : chunk;
+        dma16(sb + (long)(p >> 2) * plane_in * 2, lane_off + ch + (unsigned)((p & 3) * 8) * rs_b, lds_dst + p * 1024);
+      }
+    } else {                                                            // keys past the sequence: re-read row S - 1 (masked or never used)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int p = wave * 2 + i;
+        const unsigned ch = which == 1 ? chunk ^ (unsigned)((p & 1) << 6) : chunk;
+        const int row = min(jb * 32 + (p & 3) * 8 + (lane >> 3), S - 1);
+        dma16(sb + (long)(p >> 2) * plane_in * 2, ch + (unsigned)row * rs_b, lds_dst + p * 1024);
+      }
+    }
+  };
+  issue(0, 1, kr_lds);
+  issue(1, 1, kr_lds + HB_BYTES);
+  issue(2, 1, kr_lds + 2 * HB_BYTES);
+  issue(0, 2, vr_lds);
+
+  uint4 qf[2][4];                                        // Q planes, four 16-deep steps: d = 16 ks + 8 hi ..
+  {
+    const int qi = min(q0 + c, S - 1);
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl)
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) qf[pl][ks] = *reinterpret_cast<const uint4*>(base + pl * plane_in + (long)qi * rs + 16 * ks + 8 * hi);
+  }
+  f32x16 o[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) o[t][i] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f, a_pend = 1.f;    // m_run: the exponent reference (PSHIFT_H below the maximum it was taken from)
+  f32x16 sA, sB;
+  uint4 pA[2][2], pB[2][2];                              // P planes of the even / odd key blocks: [plane][16-key step]
+#pragma unroll
+  for (int pl = 0; pl < 2; ++pl)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) pA[pl][i] = pB[pl][i] = make_uint4(0, 0, 0, 0);
+
+  const char* kbase[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) kbase[ks] = Kr + c * 128 + (((2 * ks + hi) ^ ((c >> 1) & 7)) << 4);
+  const int j16 = lane & 15, jb1 = (j16 >> 3) & 1;
+  const char* vbase[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) vbase[t] = Vr + (4 * hi + (j16 >> 2)) * 128 + ((2 * (t ^ jb1) + (c >> 4)) << 5) + ((j16 & 3) << 3);
+
+  __builtin_amdgcn_s_waitcnt(0x0070);                    // vmcnt(0) lgkmcnt(0) as a builtin (hipcc then knows the Q loads have landed)
+  barrier_lds();
+
+  auto step = [&](auto qk_c, auto sm_c, auto mask_c, auto pv_c, auto par_c, int ks_off, int vs_off, int rem) {
+    constexpr bool QK = decltype(qk_c)::value, SM = decltype(sm_c)::value, MASK = decltype(mask_c)::value, PV = decltype(pv_c)::value;
+    constexpr int PAR = decltype(par_c)::value;
+    f32x16& s_next = PAR ? sA : sB;
+    f32x16& s_cur = PAR ? sB : sA;
+    uint4 (&p_cur)[2][2] = PAR ? pB : pA;
+    uint4 (&p_prev)[2][2] = PAR ? pA : pB;
+    if (!has_q) return;
+    uint4 kfs[2][2];                                     // [register set][plane]
+    f16x8 vfs[2][2];
+    float pv[16];
+    float m_new = 0.f;
+    auto load_group = [&](auto n_c) {
+      constexpr int n = decltype(n_c)::value;
+      if constexpr (QK) {
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) kfs[n & 1][pl] = *reinterpret_cast<const uint4*>(kbase[n] + ks_off + pl * 4096);
+      }
+      if constexpr (PV) {
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) {
+          const char* p = vbase[n & 1] + vs_off + pl * 4096 + (n >> 1) * 2048;
+          vfs[n & 1][pl] = tr_pair_h(p, p + 1024);
+        }
+      }
+    };
+    // one MFMA slot of super-group n: slot i = 0..5; even slots multiply on the S chain, odd slots on the O[n & 1] chain (term i >> 1 of the three plane
+    // pairs, smallest first: (h, l) (l, h) (h, h)); a variant without QK (or PV) has three slots
+    auto mfma_slot = [&](auto n_c, auto i_c) {
+      constexpr int n = decltype(n_c)::value, i = decltype(i_c)::value;
+      constexpr int term = (QK && PV) ? (i >> 1) : i;
+      constexpr bool on_s = QK && (!PV || (i & 1) == 0);
+      constexpr int PA = term == 1 ? 1 : 0;
+      constexpr int PB_ = term == 0 ? 1 : 0;
+      if constexpr (on_s) {
+        if constexpr (n == 0 && term == 0)
+          s_next = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, kfs[n & 1][PA]), __builtin_bit_cast(f16x8, qf[PB_][n]),
+                                                          f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        else
+          s_next = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, kfs[n & 1][PA]), __builtin_bit_cast(f16x8, qf[PB_][n]), s_next, 0, 0, 0);
+      } else {
+        o[n & 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfs[n & 1][PA], __builtin_bit_cast(f16x8, p_prev[PB_][n >> 1]), o[n & 1], 0, 0, 0);
+      }
+    };
+    auto sm_head = [&]() {
+      if (MASK) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          if ((i & 3) + 8 * (i >> 2) + 4 * hi >= rem) s_cur[i] = -INFINITY;
+      }
+      const float t0 = max3f(s_cur[0], s_cur[1], s_cur[2]), t1 = max3f(s_cur[3], s_cur[4], s_cur[5]), t2 = max3f(s_cur[6], s_cur[7], s_cur[8]);
+      const float t3 = max3f(s_cur[9], s_cur[10], s_cur[11]), t4 = max3f(s_cur[12], s_cur[13], s_cur[14]);
+      const float u0 = max3f(t0, t1, t2), u1 = max3f(t3, t4, s_cur[15]);
+      float mx = max3f(u0, u1, u1);
+      const auto y = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
+      mx = max3f(__uint_as_float(y[0]), __uint_as_float(y[1]), __uint_as_float(y[1]));
+      // deferred rescale with the fp16 range in mind: P^ = 2^(s - m_run) <= 2^RESCALE_H between moves, = 2^PSHIFT_H at the maximum right after one
+      const float mb = mx * qscale;
+      const bool need = mb > m_run + RESCALE_H;
+      m_new = need ? mb - PSHIFT_H : m_run;
+      a_pend = need ? __builtin_amdgcn_exp2f(m_run - m_new) : 1.0f;
+      m_run = m_new;
+    };
+    float psum = 0.f, ra[8], rb[8];
+    auto sm_exp1 = [&](int i) {
+      pv[i] = __builtin_amdgcn_exp2f(fmaf(s_cur[i], qscale, -m_new));
+      psum += pv[i];
+    };
+    // pair u of the sixteen probabilities -> word u & 3 of step u >> 2 of the two planes, in two halves (x = h + l)
+    auto sm_split_a = [&](int u) {
+#pragma clang fp contract(off)
+      const uint32_t hw = cvt_pk_h(pv[2 * u], pv[2 * u + 1]);
+      const f16x2_t hv = __builtin_bit_cast(f16x2_t, hw);
+      ra[u] = pv[2 * u] - (float)hv[0];
+      rb[u] = pv[2 * u + 1] - (float)hv[1];
+      (&p_cur[0][u >> 2].x)[u & 3] = hw;
+    };
+    auto sm_split_b = [&](int u) { (&p_cur[1][u >> 2].x)[u & 3] = cvt_pk_h(ra[u], rb[u]); };
+    constexpr int NSLOT = (QK ? 3 : 0) + (PV ? 3 : 0);                // MFMA slots per super-group
+    // the softmax work that rides behind slot i of super-group n (every slot ends in a scheduling fence: the order below IS the instruction order)
+    auto valu_chunk = [&](auto n_c, auto i_c) {
+      constexpr int n = decltype(n_c)::value, i = decltype(i_c)::value;
+      if constexpr (SM) {
+        if constexpr (NSLOT == 6) {
+          if constexpr (n == 0) {                          // sixteen exponentials over six slots
+            sm_exp1(2 * i); sm_exp1(2 * i + 1);
+            if constexpr (i < 2) { sm_exp1(12 + 2 * i); sm_exp1(13 + 2 * i); }
+            if constexpr (i == 5) l_run = l_run * a_pend + psum;
+          } else {                                         // sixteen half-splits over the first sixteen of the remaining eighteen
+            constexpr int gs = 6 * (n - 1) + i;
+            if constexpr (gs < 16) {
+              if constexpr ((gs & 1) == 0) sm_split_a(gs / 2);
+              else sm_split_b(gs / 2);
+            }
+          }
+        } else if constexpr (NSLOT == 3) {                 // (first / last steps: three slots per super-group)
+          if constexpr (n == 0) {
+#pragma unroll
+            for (int e = 0; e < 5; ++e) sm_exp1(5 * i + e);
+            if constexpr (i == 2) { sm_exp1(15); l_run = l_run * a_pend + psum; }
+          } else {
+            constexpr int gs = 3 * (n - 1) + i;
+            if constexpr (gs < 8) { sm_split_a(gs); sm_split_b(gs); }
+          }
+        }
+      }
+    };
+    if constexpr (PV) {
+      const float a_use = a_pend;
+      if (__builtin_amdgcn_ballot_w64(a_use != 1.0f) != 0) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) o[t][i] *= a_use;
+      }
+    }
+    if constexpr (QK || PV) load_group(std::integral_constant<int, 0>{});
+    if constexpr (SM) sm_head();
+    __builtin_amdgcn_sched_barrier(0);
+    auto slot = [&](auto n_c, auto i_c) {
+      constexpr int i = decltype(i_c)::value;
+      if constexpr (i < NSLOT) {
+        mfma_slot(n_c, i_c);
+        valu_chunk(n_c, i_c);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
+    auto group = [&](auto n_c) {
+      constexpr int n = decltype(n_c)::value;
+      if constexpr (NSLOT > 0) {
+        if constexpr (n < 3) {
+          load_group(std::integral_constant<int, n + 1>{});
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        slot(n_c, std::integral_constant<int, 0>{});
+        slot(n_c, std::integral_constant<int, 1>{});
+        slot(n_c, std::integral_constant<int, 2>{});
+        slot(n_c, std::integral_constant<int, 3>{});
+        slot(n_c, std::integral_constant<int, 4>{});
+        slot(n_c, std::integral_constant<int, 5>{});
+      }
+    };
+    group(std::integral_constant<int, 0>{});
+    group(std::integral_constant<int, 1>{});
+    group(std::integral_constant<int, 2>{});
+    group(std::integral_constant<int, 3>{});
+    if constexpr (NSLOT == 0 && SM) {                    // (a softmax alone: the single-key-block sequence and the key-split blocks)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) sm_exp1(i);
+      l_run = l_run * a_pend + psum;
+#pragma unroll
+      for (int u = 0; u < 8; ++u) { sm_split_a(u); sm_split_b(u); }
+    }
+  };
+  // end of a step: the pieces issued two steps ago have landed (at most the four of the previous step stay in flight), every wave is done with the
+  // two slots the step read; then refill them.  (The SAME protocol as turn() of vit_attention_split3_pipe_kernel, whose count is vmcnt(6) = 3 + 3 pieces
+  // per wave and step; here 2 + 2.  A fix to the ring protocol belongs in both kernels until the bf16x3 one can be retired into a shared template.)
+  auto turn = [&](int j, int ks, int vs) {
+    asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    issue(j + 4, 1, kr_lds + ks);
+    issue(j + 2, 2, vr_lds + vs);
+  };
+  using T = std::true_type;
+  using F = std::false_type;
+  using P0 = std::integral_constant<int, 0>;
+  using P1 = std::integral_constant<int, 1>;
+  constexpr int HB = HB_BYTES;
+  if (!ksplit) {
+    step(T{}, F{}, F{}, F{}, P1{}, 0, 0, 0);                                           // j = -1: QK(0)
+    turn(-1, 0, HB);
+    if (NB > 1) step(T{}, T{}, F{}, F{}, P0{}, HB, 0, 0);                              // j = 0: QK(1), softmax(0)
+    else step(F{}, T{}, T{}, F{}, P0{}, 0, 0, S);                                      //        (a single key block: softmax(0) masked)
+    turn(0, HB, 2 * HB);
+    int ks = 2 * HB, vs = 0;                                                           // step 1: K slot 2, V slot 0
+    int j = 1;
+    for (; j + 1 <= NB - 2; j += 2) {
+      step(T{}, T{}, F{}, T{}, P1{}, ks, vs, 0);
+      turn(j, ks, vs);
+      ks = ks == 2 * HB ? 0 : ks + HB;
+      vs = vs == 2 * HB ? 0 : vs + HB;
+      step(T{}, T{}, F{}, T{}, P0{}, ks, vs, 0);
+      turn(j + 1, ks, vs);
+      ks = ks == 2 * HB ? 0 : ks + HB;
+      vs = vs == 2 * HB ? 0 : vs + HB;
+    }
+    if (j <= NB - 2) {                                                                 // one more steady step (odd j)
+      step(T{}, T{}, F{}, T{}, P1{}, ks, vs, 0);
+      turn(j, ks, vs);
+      ks = ks == 2 * HB ? 0 : ks + HB;
+      vs = vs == 2 * HB ? 0 : vs + HB;
+      ++j;
+    }
+    const int rem = S - (NB - 1) * 32;
+    if (NB > 1) {
+      if (j & 1) step(F{}, T{}, T{}, T{}, P1{}, ks, vs, rem);
+      else step(F{}, T{}, T{}, T{}, P0{}, ks, vs, rem);
+      vs = vs == 2 * HB ? 0 : vs + HB;
+      ++j;
+    }
+    barrier_all();                                          // V(NB - 1) of EVERY wave has landed (and every DMA, before the block may exit)
+    if (j & 1) step(F{}, F{}, F{}, T{}, P1{}, 0, vs, 0);
+    else step(F{}, F{}, F{}, T{}, P0{}, 0, vs, 0);
+  } else {
+    const int remk = S - (NB - 1) * 32;
+    int ksj = 0, vsj = HB;                                                             // j = -1: K slot 0, V slot 1
+    for (int jj = -1; jj <= NB; ++jj) {
+      if (((jj + 1 - wave) & 3) == 0 && jj + 1 < NB) step(T{}, F{}, F{}, F{}, P1{}, ksj, vsj, 0);            // QK of my block jj + 1
+      else if (((jj - wave) & 3) == 0 && jj >= 0 && jj < NB) {                                                // softmax of my block jj
+        if (jj == NB - 1) step(F{}, T{}, T{}, F{}, P0{}, ksj, vsj, remk);
+        else step(F{}, T{}, F{}, F{}, P0{}, ksj, vsj, 0);
+      } else if (((jj - 1 - wave) & 3) == 0 && jj >= 1 && jj - 1 < NB) step(F{}, F{}, F{}, T{}, P1{}, ksj, vsj, 0);   // PV of my block jj - 1
+      if (jj <= NB - 2) turn(jj, ksj, vsj);
+      else if (jj == NB - 1) barrier_all();
+      ksj = ksj == 2 * HB ? 0 : ksj + HB;
+      vsj = vsj == 2 * HB ? 0 : vsj + HB;
+    }
+    // merge (the rings are idle: every DMA landed before the last barrier): 3 x 34 x 64 floats = 25.5 KiB of the 48
+    __syncthreads();
+    float* park = reinterpret_cast<float*>(smem);
+    if (wave > 0) {
+      float* pw = park + (wave - 1) * 34 * 64 + lane;
+      pw[0] = m_run;
+      pw[64] = l_run;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) pw[(2 + t * 16 + i) * 64] = o[t][i];
+    }
+    __syncthreads();
+    if (wave > 0) return;
+#pragma unroll 1
+    for (int w = 0; w < 3; ++w) {
+      const float* pw = park + w * 34 * 64 + lane;
+      const float mw = pw[0], lw = pw[64];
+      const float mn = fmaxf(m_run, mw);
+      const float f0 = __builtin_amdgcn_exp2f(m_run - mn), fw = __builtin_amdgcn_exp2f(mw - mn);
+      l_run = l_run * f0 + lw * fw;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[t][i] = o[t][i] * f0 + pw[(2 + t * 16 + i) * 64] * fw;
+      m_run = mn;
+    }
+  }
+
+  if (!has_q) return;
+  float l = l_run;
+  {
+    const auto y = __builtin_amdgcn_permlane32_swap(__float_as_uint(l), __float_as_uint(l), false, false);
+    l = __uint_as_float(y[0]) + __uint_as_float(y[1]);
+  }
+  const float inv = 1.0f / l;                            // (O and l both carry 2^PSHIFT_H)
+  const int qo = q0 + c;
+  if (qo < S) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {
+#pragma clang fp contract(off)
+        const int col = h * 64 + 32 * t + 8 * rq + 4 * hi;
+        const float w0 = o[t][4 * rq] * inv, w1 = o[t][4 * rq + 1] * inv, w2 = o[t][4 * rq + 2] * inv, w3 = o[t][4 * rq + 3] * inv;
+        if (v_exp3) {                                      // three bf16 planes of the output itself (a bf16x3 projection follows): v's exponents come back in
+          const int4 e = *reinterpret_cast<const int4*>(v_exp3 + col);
+          const float w4[4] = {ldexpf(w0, e.x), ldexpf(w1, e.y), ldexpf(w2, e.z), ldexpf(w3, e.w)};
+          store_split3(out2 + split3_at((long)b * S + qo, col, D, kmaj_rows), plane_out, w4);
+          continue;
+        }
+        const uint32_t h0 = cvt_pk_h(w0, w1), h1 = cvt_pk_h(w2, w3);
+        const f16x2_t a = __builtin_bit_cast(f16x2_t, h0), bb = __builtin_bit_cast(f16x2_t, h1);
+        const uint32_t l0 = cvt_pk_h(w0 - (float)a[0], w1 - (float)a[1]), l1 = cvt_pk_h(w2 - (float)bb[0], w3 - (float)bb[1]);
+        uint16_t* dst = out2 + split3_at((long)b * S + qo, col, D, kmaj_rows);
+        *reinterpret_cast<uint2*>(dst) = make_uint2(h0, h1);
+        *reinterpret_cast<uint2*>(dst + plane_out) = make_uint2(l0, l1);
+      }
+  }
+}
+
 constexpr int V2_LDS = 3 * KS_BYTES;
 
 }  // namespace
@@ -846,13 +1257,21 @@ extern "C" int pf_vit_attention_split3_v2(const void* qkv3, long plane_in, void*
   if (const char* e = getenv("PF_ATTN_DBG")) dbg = atoi(e);
   if (const char* e = getenv("PF_ATTN_LDS")) lds2 = ldsp = atoi(e);      // (bytes of dynamic LDS requested: > 80 KiB leaves ONE block per CU)
 #endif
-  static int attr_done = 0;
-  if (attr_done != lds2) {
+  // (the attribute belongs to a device: one bit per device, as in conv1x1_split3.hip -- a process that drives several GPUs sets it on each)
+  static std::atomic<unsigned long long> attr_done{0};
+#ifdef PF_ATTN_DBG
+  static std::atomic<int> attr_lds{0};
+  if (attr_lds.exchange(lds2) != lds2) attr_done.store(0, std::memory_order_release);
+#endif
+  int dev = 0;
+  hipGetDevice(&dev);
+  const unsigned long long dev_bit = 1ull << (dev & 63);
+  if (!(attr_done.load(std::memory_order_acquire) & dev_bit)) {
     const void* ks[3] = {reinterpret_cast<const void*>(vit_attention_split3_v2_kernel<1>), reinterpret_cast<const void*>(vit_attention_split3_v2_kernel<2>),
                          reinterpret_cast<const void*>(vit_attention_split3_pipe_kernel)};
     for (int i = 0; i < 3; ++i)
       if (hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, i < 2 ? lds2 : ldsp) != hipSuccess) return PF_ERR_LAUNCH;
-    attr_done = lds2;
+    attr_done.fetch_or(dev_bit, std::memory_order_release);
   }
   int qw = queries_per_wave;
   if (schedule != 1) qw = 32;                                 // the pipelined kernel: a wave = the 32 columns of its accumulator tiles
@@ -871,6 +1290,28 @@ extern "C" int pf_vit_attention_split3_v2(const void* qkv3, long plane_in, void*
                        B * Hh, dbg);
   }
 #undef ATTN_LAUNCH
+  return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
+}
+
+// C entry: see include/pf_hip.h.  The pipelined kernel on two scaled fp16 planes (vit_attention_f16x2_pipe_kernel above).
+extern "C" int pf_vit_attention_f16x2(const void* qkv2, long plane_in, const int* qk_exp, void* out, long plane_out, const int* v_exp3, int B, int S, int Hh,
+                                      void* stream) {
+  void* out2 = out;
+  if (!qkv2 || !qk_exp || !out2 || B <= 0 || S <= 0 || Hh <= 0 || plane_in < (long)B * S * Hh * 192 || plane_out < (long)B * S * Hh * 64) return PF_ERR_ARG;
+  if ((long)S * Hh * 192 * 2 >= (1L << 31)) return PF_ERR_ARG;                           // 32-bit byte offsets inside one image's rows
+  static std::atomic<unsigned long long> attr_done{0};
+  int dev = 0;
+  hipGetDevice(&dev);
+  const unsigned long long dev_bit = 1ull << (dev & 63);
+  if (!(attr_done.load(std::memory_order_acquire) & dev_bit)) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(vit_attention_f16x2_pipe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PIPE_H_LDS) != hipSuccess)
+      return PF_ERR_LAUNCH;
+    attr_done.fetch_or(dev_bit, std::memory_order_release);
+  }
+  const float qscale = 0.125f * 1.4426950408889634f;        // head_dim^-1/2 times log2(e); the head exponents join it in the kernel
+  const int n_qb = (S + 127) / 128;
+  hipLaunchKernelGGL(vit_attention_f16x2_pipe_kernel, dim3(n_qb * B * Hh), dim3(256), PIPE_H_LDS, reinterpret_cast<hipStream_t>(stream),
+                     (const uint16_t*)qkv2, plane_in, qk_exp, (uint16_t*)out2, plane_out, v_exp3, S, Hh, qscale, (long)B * S, n_qb, B * Hh);
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
 }
 

@@ -635,7 +635,8 @@ __global__ __launch_bounds__(512) void gemm_split3_persist_kernel(const pf_conv_
 // they cannot make the count pass early (the DESIGN 4i rule: never count register loads in a hand-counted wait).
 // F16 && !BARE (round 8, the ViT block linears, pf_gemm_f16x2): the same ring with the full epilogue.  The column exponents come from p.col_exp
 // (p.scale is LayerScale there); ldexp(acc, f_n) first, then bias -> act -> scale -> residual(s), stored as float32, as three bf16 row-major planes,
-// or (korder bit 16) as two fp16 chunk-major planes of y / 2^out_exp[n] for a following fp16x2 linear (fc1 -> fc2).  The epilogue still runs at the
+// or (korder bit 16) as two fp16 chunk-major planes of y / 2^out_exp[n] for a following fp16x2 linear (fc1 -> fc2), or (korder bit 32, round 10) as two
+// fp16 ROW-major planes of y / 2^out_exp[n] (q / k / v for the fp16x2 attention of csrc/attn_split3.hip).  The epilogue still runs at the
 // head of a load phase, before that phase's pieces: its bias / scale / exponent / residual loads and its stores are older than the pieces each
 // counted wait lets fly, exactly as the BARE form's exponent loads are.
 template <bool BARE, bool BL, bool F16 = false, int NSL = 2>
@@ -837,7 +838,7 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
         if (nok) fexp = *reinterpret_cast<const int4*>(reinterpret_cast<const int*>(p.scale) + (long)e_z * p.w_rows + n);
       } else if constexpr (F16) {
         if (nok) fexp = *reinterpret_cast<const int4*>(p.col_exp + n);
-        if (nok && (p.korder & 16)) oexp = *reinterpret_cast<const int4*>(p.out_exp + n);
+        if (nok && (p.korder & 48)) oexp = *reinterpret_cast<const int4*>(p.out_exp + n);
       }
       if constexpr (!BARE) {
         if (nok) {
@@ -917,6 +918,23 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
               const auto s0 = __builtin_amdgcn_permlane16_swap(hw[0], lw2[0], false, false);
               const auto s1 = __builtin_amdgcn_permlane16_swap(hw[1], lw2[1], false, false);
               if (ok) *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(p.y) + split3_at(m, ne, p.y_ld, M) + (oddg ? p.y_bstride : 0)) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+            } else if (F16 && (p.korder & 32)) {
+              // two fp16 planes of y / 2^out_exp, ROW-major (the fp16x2 attention reads token rows): a lane's share of a plane row is 8 bytes
+              const int oe[4] = {oexp.x, oexp.y, oexp.z, oexp.w};
+              uint32_t hw[2], lw2[2];
+#pragma unroll
+              for (int r = 0; r < 4; r += 2) {
+                const float t0 = ldexpf(v[h][r], -oe[r]), t1 = ldexpf(v[h][r + 1], -oe[r + 1]);
+                const _Float16 h0 = (_Float16)t0, h1 = (_Float16)t1;
+                const _Float16 l0 = (_Float16)(t0 - (float)h0), l1 = (_Float16)(t1 - (float)h1);
+                hw[r >> 1] = (uint32_t)__builtin_bit_cast(uint16_t, h0) | ((uint32_t)__builtin_bit_cast(uint16_t, h1) << 16);
+                lw2[r >> 1] = (uint32_t)__builtin_bit_cast(uint16_t, l0) | ((uint32_t)__builtin_bit_cast(uint16_t, l1) << 16);
+              }
+              if (ok) {
+                uint16_t* yp = reinterpret_cast<uint16_t*>(p.y) + (long)m * p.y_ld + n;
+                *reinterpret_cast<uint2*>(yp) = make_uint2(hw[0], hw[1]);
+                *reinterpret_cast<uint2*>(yp + p.y_bstride) = make_uint2(lw2[0], lw2[1]);
+              }
             } else if (F16 || !(p.korder & 8)) {
               if (ok) store_split3(reinterpret_cast<bf16_t*>(p.y) + split3_at(m, n, p.y_ld, 0), p.y_bstride, v[h]);
             } else {
@@ -1362,15 +1380,17 @@ extern "C" int pf_gemm_f16x2_points(const pf_conv_params* p, const int* col_exp,
 extern "C" int pf_gemm_f16x2(const pf_conv_params* p, void* stream) {
   if (!p || !p->x || !p->w || !p->y || !p->col_exp) return PF_ERR_ARG;
   const long M = (long)p->B * p->OH * p->OW;
-  if (p->KH != 1 || p->KW != 1 || p->stride != 1 || p->pad != 0 || p->shuffle > 1 || p->batch > 1 || (p->korder & ~16) != 6) return PF_ERR_ARG;
+  if (p->KH != 1 || p->KW != 1 || p->stride != 1 || p->pad != 0 || p->shuffle > 1 || p->batch > 1 || (p->korder & ~48) != 6 || (p->korder & 48) == 48)
+    return PF_ERR_ARG;
   if (p->Cin <= 0 || p->Cin % 32 || p->x_ld != p->Cin || p->Kpad != p->Cin || p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || p->w_rows < p->Cout ||
       p->w_rows % 4)
     return PF_ERR_ARG;
   if (M <= 0 || M * 64 >= (1L << 31) || (long)p->w_rows * 64 >= (1L << 31) || p->x_bstride <= 0 || p->w_bstride <= 0) return PF_ERR_ARG;
   if ((p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) return PF_ERR_ARG;
-  if (p->out_f32 && (p->korder & 16)) return PF_ERR_ARG;
+  if (p->out_f32 && (p->korder & 48)) return PF_ERR_ARG;
   if (!p->out_f32 && p->y_bstride <= 0) return PF_ERR_ARG;
   if ((p->korder & 16) && (!p->out_exp || p->y_ld != p->Cout || p->Cout % 32)) return PF_ERR_ARG;
+  if ((p->korder & 32) && (!p->out_exp || p->y_ld < p->Cout || p->y_bstride % 4 || (reinterpret_cast<size_t>(p->y) & 7))) return PF_ERR_ARG;   // 8-byte stores
   return launch_persist192_f16_linear(*p, reinterpret_cast<hipStream_t>(stream));
 }
 

@@ -41,6 +41,20 @@ def vit_f16x2_enabled(crops):
     return v == "2" or (v != "0" and crops)
 
 
+def vit_attn_f16x2_enabled():
+    """with the fp16x2 block linears (vit_f16x2_enabled): also run the attention and the projection on two scaled fp16 planes (csrc/attn_split3.hip
+    pf_vit_attention_f16x2, the projection through pf_gemm_f16x2)?  PF_VIT_ATTN_F16X2: 0 = the round-8 block (fp16x2 qkv / fc1 / fc2, bf16x3
+    attention and projection); 1 (default) = q / k / v on two fp16 planes and the fp16x2 attention, which writes the three bf16 planes of a
+    projection that stays on bf16x3; 2 = the attention's output and the projection on two fp16 planes as well.  Measured per launch at
+    8 x 1037 tokens (profiles/r10_attn_f16x2_launches.md): attention 1.54x (three bf16 planes out) / 1.59x (two fp16 planes out), the fp16x2
+    projection 0.96-0.98x of the bf16x3 one -- not faster, so it moves only on request.  Image pass, two engines, built in both orders
+    (profiles/r10_attn_f16x2_image_ab.md): 1 gains 3.0 ms over 0 in the mean of the two orders.  Read once per engine build; crops branch only.
+    -> 0, 1 (attention) or 2 (attention and projection)"""
+    import os
+    v = os.environ.get("PF_VIT_ATTN_F16X2", "1")
+    return 0 if v == "0" else 2 if v == "2" else 1
+
+
 def attention_split3_enabled():
     """float32 mode with split-precision linears: also run the ViT attention in split precision (pf_vit_attention_split3)?  PF_ATTN_SPLIT3=0 / 1"""
     import os
@@ -201,9 +215,14 @@ class BranchNet:
                 return _pc(name, bias, **kw)
         # ... and, when the op set has the fp16x2 linears (the HIP ops do; PF_VIT_F16X2=0 keeps bf16x3), qkv / fc1 / fc2 run on two fp16 planes
         # with static power-of-two scales derived from the weights (packing.pack_conv_f16x2): only those planes are packed for them.  The
-        # projection keeps the bf16x3 planes the attention writes.
+        # projection keeps the bf16x3 planes the attention writes unless the attention moves too (attn_f16x2 below).
         # (crops: this branch runs batches of crops -- the fine branch -- rather than one image per call)
         self.f16x2 = self.split3 and vit_f16x2_enabled(crops) and getattr(ops, "conv_f16x2", None) is not None
+        # ... and with them (PF_VIT_ATTN_F16X2, crops only) the attention and the projection: q / k / v and the attention output then travel as two
+        # fp16 planes as well, with static exponents (packing.vit_attn_f16x2_scales), and the projection's bf16x3 planes are not packed
+        self.attn_f16x2 = (self.f16x2 and crops and vit_attn_f16x2_enabled() != 0 and attention_split3_enabled() and pk.split3_kmajor_enabled()
+                           and getattr(ops, "vit_attention_f16x2", None) is not None)
+        self.proj_f16x2 = self.attn_f16x2 and vit_attn_f16x2_enabled() == 2
         self.blocks = []
         for i in range(self.depth):
             b = f"{v}blocks.{i}."
@@ -217,10 +236,21 @@ class BranchNet:
                                          pk.gelu_linear_bound(w1, b1, bn2)).to(dev)
             else:
                 qkv, fc1, fc2 = pc(b + "attn.qkv"), pc(b + "mlp.fc1"), pc(b + "mlp.fc2", scale=sd[b + "ls2.gamma"])
+            attn = None
+            if self.attn_f16x2:
+                attn = pk.vit_attn_f16x2_scales(sd[b + "attn.qkv.weight"], sd[b + "attn.qkv.bias"], bn1, self.heads)
+                if self.proj_f16x2:
+                    proj = pk.pack_conv_f16x2(sd[b + "attn.proj.weight"], sd[b + "attn.proj.bias"], sd[b + "ls1.gamma"], attn.v_bound).to(dev)
+                else:
+                    proj = pc(b + "attn.proj", scale=sd[b + "ls1.gamma"])
+                attn = attn.to(dev)
+            else:
+                proj = pc(b + "attn.proj", scale=sd[b + "ls1.gamma"])
             self.blocks.append(dict(
                 n1=(_g(sd, b + "norm1.weight", dev), _g(sd, b + "norm1.bias", dev)),
                 qkv=qkv,
-                proj=pc(b + "attn.proj", scale=sd[b + "ls1.gamma"]),
+                attn=attn,
+                proj=proj,
                 n2=(_g(sd, b + "norm2.weight", dev), _g(sd, b + "norm2.bias", dev)),
                 fc1=fc1,
                 fc2=fc2))
@@ -290,6 +320,10 @@ class BranchNet:
             qkv = ops.empty((3, B * S, 3 * D), torch.bfloat16, dev) if attention_split3_enabled() else ops.empty((B * S, 3 * D), dt, dev)
             if self.f16x2:                                         # LayerNorm outputs and the fc1 -> fc2 intermediate as two fp16 planes, chunk-major
                 hbuf, mid = (ops.empty((2, n // 32, B * S, 32), torch.float16, dev) for n in (D, 4 * D))
+            if self.attn_f16x2:                                    # ... and q / k / v (row-major); the attention output too when the projection follows suit
+                qkv = ops.empty((2, B * S, 3 * D), torch.float16, dev)
+                if self.proj_f16x2:
+                    att = ops.empty((2, D // 32, B * S, 32), torch.float16, dev)
         else:
             hbuf = ops.empty((B * S, D), dt, dev)
             qkv = ops.empty((B * S, 3 * D), dt, dev)
@@ -298,9 +332,18 @@ class BranchNet:
         for i, blk in enumerate(self.blocks):
             if self.f16x2:
                 ops.layernorm_f16x2(x, hbuf, blk["n1"][0], blk["n1"][1], 1e-6, blk["qkv"].in_exp)
-                ops.conv_f16x2(hbuf, blk["qkv"], qkv)
-                ops.vit_attention(qkv, att, B, S, self.heads)
-                ops.conv_split3(att, blk["proj"], x, res=x)
+                if self.attn_f16x2:
+                    ops.conv_f16x2(hbuf, blk["qkv"], qkv, out_exp=blk["attn"].out_exp)
+                    if self.proj_f16x2:
+                        ops.vit_attention_f16x2(qkv, att, B, S, self.heads, blk["attn"].qk_exp)
+                        ops.conv_f16x2(att, blk["proj"], x, res=x)
+                    else:
+                        ops.vit_attention_f16x2(qkv, att, B, S, self.heads, blk["attn"].qk_exp, v_exp=blk["attn"].v_exp)
+                        ops.conv_split3(att, blk["proj"], x, res=x)
+                else:
+                    ops.conv_f16x2(hbuf, blk["qkv"], qkv)
+                    ops.vit_attention(qkv, att, B, S, self.heads)
+                    ops.conv_split3(att, blk["proj"], x, res=x)
                 ops.layernorm_f16x2(x, hbuf, blk["n2"][0], blk["n2"][1], 1e-6, blk["fc1"].in_exp)
                 ops.conv_f16x2(hbuf, blk["fc1"], mid, act="gelu", out_exp=blk["fc2"].in_exp)
                 ops.conv_f16x2(mid, blk["fc2"], x, res=x)

@@ -538,7 +538,12 @@ class HipOps:
         p.res2 = res2.data_ptr() if res2 is not None else None
         p.res2_ld = res2.stride(-2) if res2 is not None else 0
         korder = 6
-        if y.dtype == torch.float16:                          # fp16x2 planes of y / 2^out_exp for the next fp16x2 linear, chunk-major [2, N/32, M, 32]
+        if y.dtype == torch.float16 and y.dim() == 3:         # fp16x2 planes of y / 2^out_exp, row-major [2, M, N] (q / k / v of the fp16x2 attention)
+            assert y.shape[0] == 2 and y.shape[1] == M and y.stride(2) == 1 and y.shape[2] >= pw.cout and y.stride(1) % 4 == 0
+            assert out_exp is not None and out_exp.dtype == torch.int32 and out_exp.numel() >= pw.cout
+            p.y, p.y_ld, p.y_bstride, p.out_f32, p.out_exp = y.data_ptr(), y.stride(1), y.stride(0), 0, _p(out_exp)
+            korder |= 32
+        elif y.dtype == torch.float16:                        # fp16x2 planes of y / 2^out_exp for the next fp16x2 linear, chunk-major [2, N/32, M, 32]
             assert y.is_contiguous() and tuple(y.shape) == (2, pw.cout // 32, M, 32) and pw.cout % 32 == 0
             assert out_exp is not None and out_exp.dtype == torch.int32 and out_exp.numel() >= pw.cout
             p.y, p.y_ld, p.y_bstride, p.out_f32, p.out_exp = y.data_ptr(), pw.cout, y.stride(0), 0, _p(out_exp)
@@ -561,8 +566,8 @@ class HipOps:
     @staticmethod
     def conv_f16x2(x2, pw: PackedConv, y, act=None, res=None, res2=None, out_exp=None):
         """x2 float16 planes [2, K/32, M, 32] holding x / 2^pw.in_exp (ops.layernorm_f16x2 or a previous conv_f16x2); pw from packing.pack_conv_f16x2;
-        y float32 [M, N], bfloat16 [3, M, N] (three split planes, row-major) or float16 [2, N/32, M, 32] (planes of y / 2^out_exp for the next
-        fp16x2 linear); res / res2 float32 [M, N].  csrc/gemm_split3.hip pf_gemm_f16x2; plans cached like conv_split3."""
+        y float32 [M, N], bfloat16 [3, M, N] (three split planes, row-major), float16 [2, N/32, M, 32] (planes of y / 2^out_exp for the next
+        fp16x2 linear) or float16 [2, M, N] (the same planes row-major: q / k / v of ops.vit_attention_f16x2); res / res2 float32 [M, N].  csrc/gemm_split3.hip pf_gemm_f16x2; plans cached like conv_split3."""
         key = ("f16x2", id(pw), x2.shape, y.shape, y.stride(), y.dtype, act, x2.device,
                None if res is None else (res.shape, res.stride()), None if res2 is None else (res2.shape, res2.stride()),
                None if out_exp is None else out_exp.data_ptr())
@@ -665,6 +670,26 @@ class HipOps:
         vt = torch.empty((B, heads, 64, Sp), dtype=qkv.dtype, device=qkv.device)
         check(_L.pf_qkv_split(_p(qkv), B, S, heads, _p(q), _p(k), _p(vt), Sp, 0.125, _dt(qkv), _stream()), "pf_qkv_split")
         check(_L.pf_vit_attention(_p(q), _p(k), _p(vt), _p(out), B, S, Sp, heads, _dt(qkv), _stream()), "pf_vit_attention")
+
+    @staticmethod
+    def vit_attention_f16x2(qkv2, out2, B, S, heads, qk_exp, v_exp=None):
+        """ViT attention on two scaled fp16 planes (csrc/attn_split3.hip pf_vit_attention_f16x2): qkv2 float16 [2, B*S, 3*D] from ops.conv_f16x2 with the
+        exponents of packing.vit_attn_f16x2_scales, qk_exp int32 [heads] on the device; out2 float16 [2, D/32, B*S, 32], the projection's fp16x2 input
+        (out / 2^ev), or -- with v_exp = ev int32 [D] -- bfloat16 [3, D/32, B*S, 32], the three split planes of the output for ops.conv_split3."""
+        D = heads * 64
+        if v_exp is not None:
+            if out2.dtype != torch.bfloat16 or tuple(out2.shape) != (3, D // 32, B * S, 32) or not out2.is_contiguous():
+                raise ValueError(f"vit_attention_f16x2: bad bf16x3 output planes {out2.dtype} {tuple(out2.shape)}")
+            if v_exp.dtype != torch.int32 or v_exp.numel() != D or not v_exp.is_contiguous() or v_exp.device != qkv2.device:
+                raise ValueError(f"vit_attention_f16x2: v_exp must be contiguous int32 [{D}] on {qkv2.device}")
+        if qkv2.dtype != torch.float16 or tuple(qkv2.shape) != (2, B * S, 3 * D) or not qkv2.is_contiguous():
+            raise ValueError(f"vit_attention_f16x2: qkv2 must be contiguous float16 [2, {B * S}, {3 * D}], got {qkv2.dtype} {tuple(qkv2.shape)}")
+        if v_exp is None and (out2.dtype != torch.float16 or tuple(out2.shape) != (2, D // 32, B * S, 32) or not out2.is_contiguous()):
+            raise ValueError(f"vit_attention_f16x2: bad output planes {out2.dtype} {tuple(out2.shape)}")
+        if qk_exp.dtype != torch.int32 or qk_exp.numel() != heads or not qk_exp.is_contiguous() or qk_exp.device != qkv2.device:
+            raise ValueError(f"vit_attention_f16x2: qk_exp must be contiguous int32 [{heads}] on {qkv2.device}")
+        check(_L.pf_vit_attention_f16x2(_p(qkv2), qkv2.stride(0), _p(qk_exp), _p(out2), out2.stride(0), None if v_exp is None else _p(v_exp), B, S, heads,
+                                        _stream()), "pf_vit_attention_f16x2")
 
     @staticmethod
     def vit_attention_rpb(qkv, out, B, S, heads, tab, th, tw):

@@ -352,6 +352,51 @@ def pack_conv_f16x2(weight, bias=None, scale=None, in_bound=None):
     return PackedConv(planes, bp, sp, 1, 1, cin, cout_store, cout, col_exp=f.to(torch.int32), in_exp=e)
 
 
+def linear_bound(weight, bias, in_bound):
+    """|(W x + b)[n]| <= sum_k |W[n,k]| in_bound_k + |b_n| for |x_k| <= in_bound_k (float64 [Cout])"""
+    z = weight.detach().double().cpu().abs() @ in_bound.double()
+    if bias is not None:
+        z = z + bias.detach().double().cpu().abs()
+    return z
+
+
+@dataclass
+class AttnF16x2Scales:
+    out_exp: torch.Tensor           # int32 [3 D]: the exponents the qkv GEMM divides its columns by
+    qk_exp: torch.Tensor            # int32 [heads]: E_h = eq[c] + ek[c] for every channel c of head h, what pf_vit_attention_f16x2 folds into the softmax scale
+    v_bound: torch.Tensor           # float64 [D]: bound of v's columns = bound of the attention output's channels = the projection's in_bound
+    v_exp: Optional[torch.Tensor] = None   # int32 [D]: v's column exponents (the last third of out_exp, a view)
+
+    def to(self, device):
+        self.out_exp, self.qk_exp = self.out_exp.to(device), self.qk_exp.to(device)
+        self.v_exp = self.out_exp[2 * self.v_bound.numel():]
+        return self
+
+
+def vit_attn_f16x2_scales(qkv_weight, qkv_bias, ln_bound, heads):
+    """Static exponents of q / k / v as two fp16 planes (csrc/attn_split3.hip pf_vit_attention_f16x2), from the weights alone:
+    bound_n = sum_k |W[n,k]| LNbound_k + |b_n| per qkv column (linear_bound), r_n = ceil(log2 bound_n) - 14 (bound_exponents).
+    q and k: QK^T contracts over the 64 channels of a head, and a scale that differed along the contraction would not factor out of the sum.  What
+    must be constant along it is the exponent of the PRODUCT q_c k_c, eq[c] + ek[c] = E_h, not each factor's.  So E_h = max_c (rq[c] + rk[c]), and a
+    channel's surplus E_h - rq[c] - rk[c] >= 0 is shared between its two exponents: eq[c] = rq[c] + surplus // 2, ek[c] = E_h - eq[c].  Every
+    exponent covers its column's bound (eq[c] >= rq[c], ek[c] >= rk[c]); q-hat . k-hat 2^E_h is the logit, exactly as with one exponent per head
+    and operand, and the kernel sees only E_h.  One exponent per head and operand (the head's largest column bound) is the special case that
+    wastes headroom when a small q channel meets a large k channel: such pairs keep full fp16x2 precision here.
+    v: PV contracts over keys, so every column keeps its own exponent.  An attention output channel is a convex combination of v rows (softmax
+    weights are >= 0 and sum to 1), hence |out_d| <= bound(v_d): v's column exponents ARE the projection's input exponents, and the kernel writes
+    sum_j p_j v^_jd / l with no rescaling at all."""
+    bound = linear_bound(qkv_weight, qkv_bias, ln_bound)
+    D = bound.numel() // 3
+    assert bound.numel() == 3 * D and D == heads * 64
+    r = bound_exponents(bound).long()
+    rq, rk = r[:D].reshape(heads, 64), r[D:2 * D].reshape(heads, 64)
+    E = (rq + rk).max(dim=1).values                                              # [heads]
+    eq = rq + (E[:, None] - rq - rk) // 2
+    ek = E[:, None] - eq
+    out_exp = torch.cat([eq.reshape(-1), ek.reshape(-1), r[2 * D:]]).to(torch.int32).contiguous()
+    return AttnF16x2Scales(out_exp, E.to(torch.int32).contiguous(), bound[2 * D:].clone(), out_exp[2 * D:])
+
+
 def pack_conv_transpose(weight, bias, *, dtype):
     """nn.ConvTranspose2d(kernel=stride=s, padding=0) (dpt.py:41-52): weight [Cin, Cout, s, s].
     out[b, y*s+dy, x*s+dx, co] = bias[co] + sum_ci x[b,y,x,ci] * weight[ci,co,dy,dx]  -> a GEMM with
