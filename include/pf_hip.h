@@ -192,6 +192,17 @@ int pf_vit_attention_f16x2(const void* qkv2, long plane_in, const int* qk_exp, v
  * + (xi - xj + tw - 1), cls row -> entry n - 3, cls column -> n - 2, cls x cls -> n - 1.  queries_per_wave 16, 32 or 0 (as v2).  S < 2^20. */
 int pf_vit_attention_split3_rpb(const void* qkv3, long plane_in, void* out3, long plane_out, int kmajor, int B, int S, int Hh, const float* tab,
                                 int th, int tw, int queries_per_wave, void* stream);
+/* The same BEiT attention in the bf16 mode (csrc/vit.hip, the bias form of the 32-queries-per-wave bf16 kernel behind pf_vit_attention; same
+ * reference lines as pf_vit_attention_split3_rpb): q, k, vt bf16 exactly as pf_qkv_split writes them with scale = head_dim^-1/2 (Q*scale
+ * [B,Hh,S,64], K [B,Hh,S,64], V^T [B,Hh,64,Sp], Sp % 64 == 0, Sp >= S), out bf16 [B*S][Hh*64]; tab float32 [Hh][(2 th - 1)(2 tw - 1) + 3] as
+ * above (interpolated, times log2(e)): the kernel forms q.k * log2(e) + tab[h][idx(i, j)] in float32 (the bias is never rounded to bf16) and runs
+ * its online softmax on those base-2 logits.  Refused (PF_ERR_ARG): null pointers, S != th * tw + 1, tw < 4, S >= 2^20, Sp not a multiple of 64 or
+ * < S, a table slice that does not fit the LDS.  pf_vit_attention is unchanged. */
+int pf_vit_attention_rpb_bf16(const void* q, const void* k, const void* vt, void* out, int B, int S, int Sp, int Hh, const float* tab, int th, int tw,
+                              void* stream);
+/* LDS bytes one block of that kernel reserves: the 32 KiB of K / V^T stages + the largest table slice a 128-query block stages ((y_hi - y_lo + th)
+ * (2 tw - 1) + 3 entries, rounded to 16 bytes); -1 for a shape pf_vit_attention_rpb_bf16 refuses.  No launch, no GPU (host-side tests). */
+int pf_vit_attention_rpb_bf16_lds_bytes(int S, int th, int tw);
 /* float32 [rows][x_ld] -> three bf16 planes [3][rows][y_ld], plane stride `plane` elements (the split producers fuse into their stores) */
 int pf_split3(const float* x, int x_ld, void* y, int y_ld, long plane, long rows, int cols, void* stream);
 
@@ -206,6 +217,11 @@ int pf_patch_im2col_norm(const float* img, int B, int H, int W, int patch, const
 /* readout 'project' operand rows (MiDaS utils ProjectReadout, the act_postprocess*.0 of the core loaded at midas.py:340): x [B*S][x_ld] float32
  * token rows (cls first) -> y[b*(S-1) + t] = [x[b*S + 1 + t][0:D] | x[b*S][0:D]] (y_ld >= 2 D).  D, x_ld, y_ld multiples of 4; 16-byte pointers. */
 int pf_readout_concat(const float* x, int x_ld, int B, int S, int D, float* y, int y_ld, void* stream);
+/* The bf16 mode's forms of those two (csrc/beit_bf16.hip; same reference lines): pf_patch_im2col_norm_bf16 writes bf16 rows [..][ld] -- the float32
+ * kernel's value rounded once to nearest even, padding columns zero; pf_readout_concat_bf16 copies bf16 token rows x [B*S][x_ld] into bf16 rows y
+ * [B*(S-1)][y_ld] = [token | cls].  D, x_ld, y_ld multiples of 8 there; 16-byte pointers.  Refusals as the float32 forms (PF_ERR_ARG). */
+int pf_patch_im2col_norm_bf16(const float* img, int B, int H, int W, int patch, const float* mean3, const float* std3, void* out, int ld, void* stream);
+int pf_readout_concat_bf16(const void* x, int x_ld, int B, int S, int D, void* y, int y_ld, void* stream);
 /* tokens[b,0,:] = cls + pos[0]; tokens[b,1+t,:] = emb[b*(S-1)+t,:] + pos[1+t]  (vision_transformer.py:222-223) */
 int pf_assemble_tokens(const void* emb, void* tokens, const float* cls, const float* pos, int B, int S, int D, int dtype,
                        void* stream);

@@ -76,6 +76,9 @@ SIGNATURES = {
     "pf_vit_attention_split3_rpb": [vp, cl, vp, cl, ci, ci, ci, ci, vp, ci, ci, ci, vp],
     "pf_patch_im2col_norm": [vp, ci, ci, ci, ci, vp, vp, vp, ci, vp],
     "pf_readout_concat": [vp, ci, ci, ci, ci, vp, ci, vp],
+    "pf_vit_attention_rpb_bf16": [vp, vp, vp, vp, ci, ci, ci, ci, vp, ci, ci, vp],
+    "pf_patch_im2col_norm_bf16": [vp, ci, ci, ci, ci, vp, vp, vp, ci, vp],
+    "pf_readout_concat_bf16": [vp, ci, ci, ci, ci, vp, ci, vp],
     "pf_conv_winograd_fused": [C.POINTER(ConvParams), vp, ci, ci, vp],
     "pf_conv_winograd_fused_timed": [C.POINTER(ConvParams), vp, ci, ci, ci, C.POINTER(cf), vp],
     "pf_attractor": [vp, ci, ci, ci, cf, ci, ci, vp, ci, ci, vp, ci, ci, ci, ci, vp],
@@ -97,7 +100,7 @@ SIGNATURES = {
     "pf_depth_metrics": [vp, ci, ci, vp, ci, ci, vp, vp, cf, cf, ci, ci, ci, ci, vp, vp],
 }
 NON_STATUS = ("pf_last_error", "pf_version", "pf_percentile_workspace_bytes", "pf_conv_winograd_fused_supported", "pf_gemm_split3_route",
-              "pf_wino_f16x2_scratch_bytes", "pf_conv_winograd_f16x2_supported")   # entry points that do not return a status
+              "pf_wino_f16x2_scratch_bytes", "pf_conv_winograd_f16x2_supported", "pf_vit_attention_rpb_bf16_lds_bytes")   # entry points that do not return a status
 
 _lib = None
 
@@ -130,6 +133,8 @@ def load():
     lib.pf_wino_f16x2_scratch_bytes.argtypes = [ci, ci]
     lib.pf_conv_winograd_f16x2_supported.restype = ci                 # 1 / 0, not a status
     lib.pf_conv_winograd_f16x2_supported.argtypes = [C.POINTER(ConvParams), ci, ci, C.c_long]
+    lib.pf_vit_attention_rpb_bf16_lds_bytes.restype = ci              # bytes (or -1), not a status
+    lib.pf_vit_attention_rpb_bf16_lds_bytes.argtypes = [ci, ci, ci]
     _lib = lib
     return lib
 

@@ -1,0 +1,74 @@
+// bf16 forms of the two MiDaS BEiT-L helper kernels of csrc/beit.hip (the core's compute_dtype="bf16" mode): the normalised P x P patch im2col
+// and the readout-'project' rows [token | cls] with bfloat16 outputs, so that the patch-embedding GEMM and the readout linear read bf16 like every
+// other bf16 GEMM of the engine.  The im2col value is the float32 kernel's expression rounded once to nearest even; the readout rows are copies.
+#include "pf_common.h"
+#include "../../include/pf_hip.h"
+
+namespace {
+
+struct Norm3 {
+  float mean[3], stdv[3];
+};
+
+// out[(b,ty,tx)][(ky*P+kx)*3 + c] = bf16((img[b,c,ty*P+ky,tx*P+kx] - mean[c]) / std[c]), columns 3 P^2 .. ld-1 zero
+__global__ void patch_im2col_norm_bf16_kernel(const float* __restrict__ img, int B, int H, int W, int P, Norm3 n, bf16_t* __restrict__ out, int ld) {
+  const int th = H / P, tw = W / P, K = 3 * P * P;
+  const long total = (long)B * th * tw * ld;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int k = (int)(i % ld);
+    const long row = i / ld;
+    float v = 0.f;
+    if (k < K) {
+      const int c = k % 3, kk = k / 3, kx = kk % P, ky = kk / P;
+      const int tx = (int)(row % tw), ty = (int)((row / tw) % th), b = (int)(row / ((long)tw * th));
+      const float px = img[(((long)b * 3 + c) * H + (ty * P + ky)) * W + (tx * P + kx)];
+      v = (px - n.mean[c]) / n.stdv[c];
+    }
+    out[i] = f2bf(v);
+  }
+}
+
+// y[b*T + t][0:D] = x[b*S + 1 + t][0:D], y[b*T + t][D:2D] = x[b*S][0:D]  (T = S - 1; 16-byte granules of eight bf16, D % 8 == 0)
+__global__ void readout_concat_bf16_kernel(const bf16_t* __restrict__ x, int x_ld, int B, int S, int D, bf16_t* __restrict__ y, int y_ld) {
+  const int D8 = D / 8, T = S - 1;
+  const long total = (long)B * T * 2 * D8;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % (2 * D8));
+    const long row = i / (2 * D8);
+    const int b = (int)(row / T), t = (int)(row - (long)b * T);
+    const long src = c < D8 ? (long)b * S + 1 + t : (long)b * S;
+    const int col = (c < D8 ? c : c - D8) * 8;
+    *reinterpret_cast<uint4*>(y + row * y_ld + 8 * c) = *reinterpret_cast<const uint4*>(x + src * x_ld + col);
+  }
+}
+
+inline int grid_for(long n, int block) {
+  long g = (n + block - 1) / block;
+  return (int)(g < 8192 ? (g > 0 ? g : 1) : 8192);
+}
+
+}  // namespace
+
+extern "C" int pf_patch_im2col_norm_bf16(const float* img, int B, int H, int W, int patch, const float* mean3, const float* std3, void* out, int ld,
+                                         void* stream) {
+  if (!img || !out || !mean3 || !std3 || B <= 0 || patch <= 0 || H % patch || W % patch || ld < 3 * patch * patch) return PF_ERR_ARG;
+  Norm3 n;
+  for (int c = 0; c < 3; ++c) {
+    if (!(std3[c] != 0.f)) return PF_ERR_ARG;
+    n.mean[c] = mean3[c];
+    n.stdv[c] = std3[c];
+  }
+  const long total = (long)B * (H / patch) * (W / patch) * ld;
+  hipLaunchKernelGGL(patch_im2col_norm_bf16_kernel, dim3(grid_for(total, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), img, B, H, W, patch, n,
+                     (bf16_t*)out, ld);
+  return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
+}
+
+extern "C" int pf_readout_concat_bf16(const void* x, int x_ld, int B, int S, int D, void* y, int y_ld, void* stream) {
+  if (!x || !y || B <= 0 || S < 2 || D <= 0 || D % 8 || x_ld % 8 || y_ld % 8 || x_ld < D || y_ld < 2 * D) return PF_ERR_ARG;
+  if (((uintptr_t)x | (uintptr_t)y) & 15) return PF_ERR_ARG;
+  const long total = (long)B * (S - 1) * (D / 4);
+  hipLaunchKernelGGL(readout_concat_bf16_kernel, dim3(grid_for(total, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), (const bf16_t*)x, x_ld, B, S,
+                     D, (bf16_t*)y, y_ld);
+  return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
+}

@@ -445,11 +445,35 @@ __global__ __launch_bounds__(256, 2) void vit_attention_kernel(const T* __restri
 // slot swizzle plus the two 8-byte halves of a slot swapped for rows 16..31 (mod 32), which makes the 8-byte
 // fragment reads of a 32-lane group hit 32 distinct 8-byte bank pairs.
 // ---------------------------------------------------------------------------------------------
+//
+// RPB = true (pf_vit_attention_rpb_bf16; BEiT, the bf16 mode of the MiDaS DPT_BEiT_L_384 core): the base-2 logits become
+// s * log2(e) + tab[h][idx(i, j)] (q already carries head_dim^-1/2; tab pre-multiplied by log2(e), float32, never rounded), idx as in
+// csrc/attn_split3.hip: patch x patch (yi - yj + th - 1)(2 tw - 1) + (xi - xj + tw - 1), cls row / cls column / cls x cls the last three
+// entries.  The block copies the rows of its head's table that its 128 queries can reach (grid rows y_lo .. y_hi -> (y_hi - y_lo + th)
+// (2 tw - 1) entries, then the three cls entries) into dynamic LDS behind the 32 KiB of stages: 7.1 KB at 24 x 32, 39 KiB per block in
+// all.  Index arithmetic per QUAD of consecutive keys (one reciprocal multiply for the grid row of its first key, then a compare /
+// select per key for the one row wrap a quad can hold: tw >= 4), one 4-byte LDS gather per logit; the cls key (tile 0 only) and the cls
+// query (wave 0 of block 0 only) are patched in wave-uniform branches, padded keys are clamped and masked in the last tile only.
+// RPB = false is the unchanged kernel: no table, no dynamic LDS, logits in natural units until the exponent's fma.
+// ---------------------------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
+struct Rpb32Args {
+  const float* tab;   // [Hh][ntab], ntab = (2 th - 1)(2 tw - 1) + 3
+  int th, tw;
+};
+
+__device__ __forceinline__ Rpb32Args rpb32_of() { return Rpb32Args{nullptr, 0, 0}; }
+__device__ __forceinline__ Rpb32Args rpb32_of(Rpb32Args a) { return a; }
+
+// The kernel itself is the template, and the table arguments are a parameter pack that is EMPTY for RPB = false: that instantiation then has
+// the parent kernel's exact signature and kernel-argument segment, and compiles to the same instructions (a body inlined into two wrappers, or
+// one more unused argument, both changed its code).
+template <bool RPB, typename... R>
 __global__ __launch_bounds__(256) void vit_attention32_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                               const bf16_t* __restrict__ vt, bf16_t* __restrict__ out, int B,
-                                                              int S, int Sp, int Hh) {
+                                                              int S, int Sp, int Hh, R... rpb_args) {
+  const Rpb32Args rpb = rpb32_of(rpb_args...);
   __shared__ __attribute__((aligned(16))) char lds[2 * 2 * 64 * 128];   // [stage][K | V^T][64 rows][128 B]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 31, fh = lane >> 5;
@@ -501,6 +525,31 @@ __global__ __launch_bounds__(256) void vit_attention32_kernel(const bf16_t* __re
 
   const int ntiles = (S + 63) / 64;
   gload(0);
+
+  // RPB: this block's slice of its head's table -> LDS (visible after the barrier below), and the lane's query term of the index, in BYTES:
+  // entry (query i, key j > 0) = qoff - 4 (yj (tw - 1) + j - 1), yj = (j - 1) / tw
+  extern __shared__ __attribute__((aligned(16))) char rpb_lds[];
+  int qoff = 0, cls_off = 0, tw4 = 0, twm4 = 0;
+  float inv_tw = 0.f;
+  bool cls_wave = false;
+  if constexpr (RPB) {
+    const int th = rpb.th, tw = rpb.tw, wq = 2 * tw - 1, ntab = (2 * th - 1) * wq + 3;
+    const int qb0 = blockIdx.x * 128;
+    const int y_lo = (max(qb0, 1) - 1) / tw, y_hi = (max(min(qb0 + 128, S) - 1, 1) - 1) / tw;
+    const int nsub = (y_hi - y_lo + th) * wq;
+    const float* src = rpb.tab + (long)h * ntab;
+    float* dst = reinterpret_cast<float*>(rpb_lds);
+    for (int i = tid; i < nsub; i += 256) dst[i] = src[y_lo * wq + i];
+    if (tid < 3) dst[nsub + tid] = src[ntab - 3 + tid];
+    const int pi = max(qi - 1, 0), yi = pi / tw, xi = pi - yi * tw;          // (the cls query computes query 1's entries: in range; patched below)
+    qoff = 4 * ((yi - y_lo + th - 1) * wq + xi + tw - 1);
+    cls_off = 4 * nsub;
+    tw4 = 4 * tw;
+    twm4 = 4 * (tw - 1);
+    inv_tw = 1.0f / (float)tw;
+    cls_wave = __builtin_amdgcn_readfirstlane(q0) == 0;                                                     // wave-uniform: the wave that holds the cls query (its lane 0 and 32)
+  }
+
   lstore(0);
   __syncthreads();
   const int kswz = (fr >> 1) & 7;          // fragment rows are f*32 + fr
@@ -532,15 +581,48 @@ __global__ __launch_bounds__(256) void vit_attention32_kernel(const bf16_t* __re
           if (key >= S) sc[f][r] = -INFINITY;
         }
     }
+    constexpr float LOG2E = 1.4426950408889634f;
+    f32x16_t bz[2];
+    if constexpr (RPB) {
+      // bz <- the bias of every logit; the biased base-2 logit is fma(sc, log2(e), bz), and the exponent below folds the running maximum into the
+      // same fma (bz - m), so every probability is rounded exactly as in the unbiased kernel: an all-zero table gives its results bit for bit
+      const float* cls3 = reinterpret_cast<const float*>(rpb_lds + cls_off);
+      const bool key0 = kt == 0 && fh == 0;                 // register 0 of fragment 0 is the cls key
+      const int pb = kt * 64 + 4 * fh - 1;                  // patch index p = key - 1 of register 0 of fragment 0 (-1: the cls key)
+      auto add_bias = [&](auto clsq_c) {
+        constexpr bool CLSQ = decltype(clsq_c)::value;      // this wave holds the cls query (lanes fr == 0)
+        const bool is_clsq = CLSQ && fr == 0;
+        const float row_v = cls3[0], key0_v = is_clsq ? cls3[2] : cls3[1];
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+          for (int jq = 0; jq < 4; ++jq) {
+            const int p0 = pb + 32 * f + 8 * jq;
+            const int y0 = __float2int_rz(((float)p0 + 0.5f) * inv_tw);      // exact for p0 < 2^20 (host check); p0 = -1 -> 0
+            const int wrap_at = tw4 - 4 * (p0 - y0 * rpb.tw);                // 4 (tw - x0): byte step of the first key in the next grid row
+            const int l0 = qoff - y0 * twm4 - 4 * p0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              int li = l0 - 4 * i - (4 * i >= wrap_at ? twm4 : 0);
+              li = max(li, 0);                              // keys past the sequence (last tile, masked): keep the gather inside the slice
+              float bv = *reinterpret_cast<const float*>(rpb_lds + li);
+              if constexpr (CLSQ) bv = is_clsq ? row_v : bv;
+              if (f == 0 && jq == 0 && i == 0) bv = key0 ? key0_v : bv;
+              bz[f][4 * jq + i] = bv;
+            }
+          }
+      };
+      if (cls_wave) add_bias(std::true_type{});
+      else add_bias(std::false_type{});
+    }
     float mx = -INFINITY;
 #pragma unroll
     for (int f = 0; f < 2; ++f)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sc[f][r]);
+      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, RPB ? fmaf(sc[f][r], LOG2E, bz[f][r]) : sc[f][r]);   // (masked keys: -inf either way)
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
     // statistics in the base-2 domain: exp(x - m) = exp2(x*log2e - m*log2e); one fma + one v_exp_f32 per score
-    constexpr float LOG2E = 1.4426950408889634f;
-    const float m_new = fmaxf(m_run, mx * LOG2E);
+    const float m_new = fmaxf(m_run, RPB ? mx : mx * LOG2E);
     const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
     m_run = m_new;
     float psum = 0.f;
@@ -548,7 +630,7 @@ __global__ __launch_bounds__(256) void vit_attention32_kernel(const bf16_t* __re
     for (int f = 0; f < 2; ++f)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float pe = __builtin_amdgcn_exp2f(fmaf(sc[f][r], LOG2E, -m_new));
+        const float pe = __builtin_amdgcn_exp2f(fmaf(sc[f][r], LOG2E, RPB ? bz[f][r] - m_new : -m_new));
         sc[f][r] = pe;
         psum += pe;
       }
@@ -592,6 +674,18 @@ __global__ __launch_bounds__(256) void vit_attention32_kernel(const bf16_t* __re
       for (int j = 0; j < 4; ++j)
         store4(dst + fd * 32 + 8 * j, o[fd][4 * j] * inv, o[fd][4 * j + 1] * inv, o[fd][4 * j + 2] * inv, o[fd][4 * j + 3] * inv);
   }
+}
+
+// RPB = false: 146 + 32 registers, two blocks per CU; the bias form must stay inside 256 (two blocks per CU: 2 x 39 KiB of LDS at 24 x 32)
+// the largest table slice a 128-query block of vit_attention32_kernel<true> stages, in entries (the three cls entries included)
+inline long rpb32_slice_entries(int S, int th, int tw) {
+  int rows = 0;
+  for (int qb0 = 0; qb0 < S; qb0 += 128) {
+    const int y_lo = ((qb0 > 1 ? qb0 : 1) - 1) / tw, last = (qb0 + 128 < S ? qb0 + 128 : S) - 1;
+    const int y_hi = ((last > 1 ? last : 1) - 1) / tw;
+    rows = rows > y_hi - y_lo + th ? rows : y_hi - y_lo + th;
+  }
+  return (long)rows * (2 * tw - 1) + 3;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1047,9 +1141,32 @@ extern "C" int pf_vit_attention(const void* q, const void* k, const void* vt, vo
   dim3 grid((S + 63) / 64, B * Hh);
   static int old_attn = -1;
   if (old_attn < 0) { const char* e = getenv("PF_ATTN_OLD"); old_attn = (e && e[0] == '1') ? 1 : 0; }
-  if (dtype == PF_DTYPE_BF16 && !old_attn) hipLaunchKernelGGL(vit_attention32_kernel, dim3((S + 127) / 128, B * Hh), dim3(256), 0, ST(stream), (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)vt, (bf16_t*)out, B, S, Sp, Hh);
+  if (dtype == PF_DTYPE_BF16 && !old_attn) hipLaunchKernelGGL(vit_attention32_kernel<false>, dim3((S + 127) / 128, B * Hh), dim3(256), 0, ST(stream), (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)vt, (bf16_t*)out, B, S, Sp, Hh);
   else if (dtype == PF_DTYPE_BF16) hipLaunchKernelGGL(vit_attention_kernel<bf16_t>, grid, dim3(256), 0, ST(stream), (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)vt, (bf16_t*)out, B, S, Sp, Hh);
   else hipLaunchKernelGGL(vit_attention_kernel<float>, grid, dim3(256), 0, ST(stream), (const float*)q, (const float*)k, (const float*)vt, (float*)out, B, S, Sp, Hh);
+  return ok();
+}
+
+extern "C" int pf_vit_attention_rpb_bf16_lds_bytes(int S, int th, int tw) {
+  if (th <= 0 || tw < 4 || (long)th * tw + 1 != S || S >= (1 << 20)) return -1;
+  return 2 * 2 * 64 * 128 + (int)((rpb32_slice_entries(S, th, tw) * 4 + 15) / 16 * 16);
+}
+
+extern "C" int pf_vit_attention_rpb_bf16(const void* q, const void* k, const void* vt, void* out, int B, int S, int Sp, int Hh, const float* tab, int th,
+                                         int tw, void* stream) {
+  if (!q || !k || !vt || !out || !tab || B <= 0 || Hh <= 0 || Sp % 64 || Sp < S) return PF_ERR_ARG;
+  if (th <= 0 || tw < 4 || (long)th * tw + 1 != S || S >= (1 << 20)) return PF_ERR_ARG;   // cls + the th x tw grid; the key-row division is exact below 2^20;
+  const int lds = pf_vit_attention_rpb_bf16_lds_bytes(S, th, tw);                          // a quad of keys crosses at most one grid row
+  const int dyn = lds - 2 * 2 * 64 * 128;
+  if (lds > 160 * 1024) return PF_ERR_ARG;
+  static int attr_dyn = 0;
+  if (lds > 64 * 1024 && attr_dyn < dyn) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(vit_attention32_kernel<true, Rpb32Args>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn) != hipSuccess)
+      return PF_ERR_LAUNCH;
+    attr_dyn = dyn;
+  }
+  hipLaunchKernelGGL((vit_attention32_kernel<true, Rpb32Args>), dim3((S + 127) / 128, B * Hh), dim3(256), dyn, ST(stream), (const bf16_t*)q, (const bf16_t*)k,
+                     (const bf16_t*)vt, (bf16_t*)out, B, S, Sp, Hh, Rpb32Args{tab, th, tw});
   return ok();
 }
 

@@ -425,6 +425,16 @@ class BranchNet:
         return depth, [x_d0, r4, r3, r2, r1, out_conv]
 
 
+def _accepts_dtype(fn):
+    """does a provider's forward_nhwc take the compute dtype (midas_core.MidasBeitCore does; an older provider object may not)?"""
+    import inspect
+    try:
+        ps = inspect.signature(fn).parameters
+    except (TypeError, ValueError):
+        return False
+    return "dtype" in ps or any(p.kind == p.VAR_KEYWORD for p in ps.values())
+
+
 class ExternalCoreBranchNet:
     """ZoeDepth branch whose relative-depth core is EXTERNAL (type 'ZoeDepth': MiDaS DPT_BEiT_L_384, BASELINE configs[4]).
 
@@ -449,11 +459,14 @@ class ExternalCoreBranchNet:
     def forward(self, ops, img, taps=None):
         dt, dev = self.dtype, self.device
         if hasattr(self.provider, "forward_nhwc"):               # a native core (midas_core.MidasBeitCore): NHWC straight into the clb buffer
-            if dt != F32:
-                raise NotImplementedError("the native MiDaS core runs in float32 only (compute_dtype='fp32')")
             B, _, H, W = img.shape
             clb = self.head.new_clb_buffer(ops, B, H, W)
-            _, feats = self.provider.forward_nhwc(ops, img, out_conv=clb[..., :32], rel=clb[..., 32 + self.head.emb:])
+            if dt == F32:
+                _, feats = self.provider.forward_nhwc(ops, img, out_conv=clb[..., :32], rel=clb[..., 32 + self.head.emb:])
+            elif _accepts_dtype(self.provider.forward_nhwc):
+                _, feats = self.provider.forward_nhwc(ops, img, out_conv=clb[..., :32], rel=clb[..., 32 + self.head.emb:], dtype=dt)
+            else:
+                raise NotImplementedError(f"this relative-depth core's forward_nhwc takes no dtype: it runs in float32 only (compute_dtype='fp32'), not {dt}")
             btl, blocks = feats[0], feats[1:5]
             x_d0 = ops.empty(btl.shape[:3] + (self.C,), dt, dev)
             ops.conv(btl, self.conv2, x_d0)

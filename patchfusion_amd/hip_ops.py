@@ -711,11 +711,41 @@ class HipOps:
                                              int(_env("PF_ATTN_QW", "0")), _stream()), "pf_vit_attention_split3_rpb")
 
     @staticmethod
+    def vit_attention_rpb_bf16(qkv, out, B, S, heads, tab, th, tw):
+        """The same BEiT attention in the bf16 mode (csrc/vit.hip pf_vit_attention_rpb_bf16): qkv bfloat16 [B*S, 3*D] rows of the QKV GEMM -> out
+        bfloat16 [B*S, D]; pf_qkv_split (q scaled by head_dim^-1/2, rounded to bf16) + the biased 32-queries-per-wave kernel.  tab float32 as above."""
+        D = heads * 64
+        if qkv.dtype != torch.bfloat16 or tuple(qkv.shape) != (B * S, 3 * D) or not qkv.is_contiguous():
+            raise ValueError(f"vit_attention_rpb_bf16: qkv must be contiguous bfloat16 [{B * S}, {3 * D}], got {qkv.dtype} {tuple(qkv.shape)}")
+        if out.dtype != torch.bfloat16 or tuple(out.shape) != (B * S, D) or not out.is_contiguous() or out.device != qkv.device:
+            raise ValueError(f"vit_attention_rpb_bf16: out must be contiguous bfloat16 [{B * S}, {D}] on {qkv.device}, got {out.dtype} {tuple(out.shape)}")
+        if S != th * tw + 1 or tw < 4:
+            raise ValueError(f"vit_attention_rpb_bf16: S = {S} must be th * tw + 1 = {th * tw + 1} with tw >= 4")
+        ntab = (2 * th - 1) * (2 * tw - 1) + 3
+        if tab.dtype != torch.float32 or tuple(tab.shape) != (heads, ntab) or not tab.is_contiguous() or tab.device != qkv.device:
+            raise ValueError(f"vit_attention_rpb_bf16: tab must be contiguous float32 [{heads}, {ntab}] on {qkv.device}")
+        Sp = (S + 63) // 64 * 64
+        q = torch.empty((B, heads, S, 64), dtype=qkv.dtype, device=qkv.device)
+        k = torch.empty_like(q)
+        vt = torch.empty((B, heads, 64, Sp), dtype=qkv.dtype, device=qkv.device)
+        check(_L.pf_qkv_split(_p(qkv), B, S, heads, _p(q), _p(k), _p(vt), Sp, 0.125, 1, _stream()), "pf_qkv_split")
+        check(_L.pf_vit_attention_rpb_bf16(_p(q), _p(k), _p(vt), _p(out), B, S, Sp, heads, _p(tab), th, tw, _stream()), "pf_vit_attention_rpb_bf16")
+
+    @staticmethod
     def patch_im2col_norm(img, out, patch, mean, std):
-        """img float32 [B,3,H,W] -> out float32 [B*(H/patch)*(W/patch), ld >= 3 patch^2] rows of (x - mean[c]) / std[c] (K order ky, kx, c)"""
+        """img float32 [B,3,H,W] -> out float32 (or bfloat16: the bf16 mode, rounded once) [B*(H/patch)*(W/patch), ld >= 3 patch^2] rows of
+        (x - mean[c]) / std[c] (K order ky, kx, c)"""
         B, Ci, H, W = img.shape
         if img.dtype != torch.float32 or not img.is_contiguous() or Ci != 3 or H % patch or W % patch:
             raise ValueError(f"patch_im2col_norm: img must be contiguous float32 [B,3,H,W] with H, W multiples of {patch}")
+        if out.dtype == torch.bfloat16:
+            if out.dim() != 2 or out.shape[0] != B * (H // patch) * (W // patch) or out.shape[1] < 3 * patch * patch or out.stride(1) != 1 \
+                    or out.device != img.device:
+                raise ValueError(f"patch_im2col_norm: bad output {out.dtype} {tuple(out.shape)}")
+            m3, s3 = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+            check(_L.pf_patch_im2col_norm_bf16(_p(img), B, H, W, patch, C.cast(m3, C.c_void_p), C.cast(s3, C.c_void_p), _p(out), out.stride(0),
+                                               _stream()), "pf_patch_im2col_norm_bf16")
+            return
         if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B * (H // patch) * (W // patch) or out.shape[1] < 3 * patch * patch \
                 or out.stride(1) != 1:
             raise ValueError(f"patch_im2col_norm: bad output {out.dtype} {tuple(out.shape)}")
@@ -725,8 +755,15 @@ class HipOps:
 
     @staticmethod
     def readout_concat(x, y, B, S):
-        """x float32 [B*S, D] token rows (row stride >= D) -> y float32 [B*(S-1), 2D] rows [token | cls of its image]"""
+        """x float32 [B*S, D] token rows (row stride >= D) -> y float32 [B*(S-1), 2D] rows [token | cls of its image]; both bfloat16 in the bf16 mode"""
         D = x.shape[1]
+        if x.dtype == torch.bfloat16:
+            if y.dtype != torch.bfloat16 or x.shape[0] != B * S or x.stride(1) != 1 or y.stride(1) != 1 or x.device != y.device:
+                raise ValueError("readout_concat: bfloat16 row-major operands on one device required")
+            if tuple(y.shape) != (B * (S - 1), 2 * D) or D % 8 or x.stride(0) % 8 or y.stride(0) % 8 or (x.data_ptr() | y.data_ptr()) & 15:
+                raise ValueError(f"readout_concat: bad shapes / strides / alignment x {tuple(x.shape)} y {tuple(y.shape)}")
+            check(_L.pf_readout_concat_bf16(_p(x), x.stride(0), B, S, D, _p(y), y.stride(0), _stream()), "pf_readout_concat_bf16")
+            return
         if x.dtype != torch.float32 or y.dtype != torch.float32 or x.shape[0] != B * S or x.stride(1) != 1 or y.stride(1) != 1:
             raise ValueError("readout_concat: float32 row-major operands required")
         if tuple(y.shape) != (B * (S - 1), 2 * D) or D % 4 or x.stride(0) % 4 or y.stride(0) % 4 or (x.data_ptr() | y.data_ptr()) & 15:

@@ -6,6 +6,10 @@ un-vendored torch.hub repository (midas.py:340).  ``MidasBeitCore`` is an opt-in
 plain-PyTorch restatement tests/midas_beit_ref.py, which is itself pinned against transformers' BEiT and the reference's own MidasCore
 hooks -- not against MiDaS, whose source is not available.
 
+compute_dtype="fp32" (below) is the float32-grade route; compute_dtype="bf16" is the fast mode: the same sequence on plain bfloat16 tensors
+(LayerNorm -> bf16 GEMM -> pf_qkv_split + pf_vit_attention_rpb_bf16 -> bf16 GEMM with the residual ...), float32 accumulation, statistics and
+bias tables.
+
 Per crop: PrepForMidas normalisation fused into the 16x16 patch im2col (pf_patch_im2col_norm), 24 BEiT blocks whose linears run as
 float32-grade split GEMMs (pf_gemm_split3) and whose attention adds the per-layer relative-position bias inside the split attention kernel
 (pf_vit_attention_split3_rpb), the readout-'project' rows [token | cls] (pf_readout_concat) through Linear(2D -> D) + GELU at the four hook
@@ -15,6 +19,7 @@ import torch
 from . import packing as pk
 
 F32 = torch.float32
+BF16 = torch.bfloat16
 
 # name -> depth, width, heads, hook blocks, reassemble widths, pretrain window, decoder features, input size (H, W)
 MIDAS_BEIT_SETTINGS = {
@@ -58,11 +63,13 @@ def _ignored(k):
 
 class MidasBeitCore:
     """Feature provider: ``core(img [B,3,H,W] float32 in [0,1]) -> (rel_depth [B,H,W], [l4_rn, r4, r3, r2, r1, out_conv])`` NCHW, and
-    ``forward_nhwc(ops, img, out_conv=None, rel=None)`` for engine.ExternalCoreBranchNet (writes out_conv / rel_depth into its buffers).
+    ``forward_nhwc(ops, img, out_conv=None, rel=None, dtype=None)`` for engine.ExternalCoreBranchNet (writes out_conv / rel_depth into its
+    buffers; ``dtype`` torch.float32 (default) or torch.bfloat16 = the branch's compute dtype).
 
     ``settings``: a name of MIDAS_BEIT_SETTINGS or a dict of the same fields.  Weights arrive through ``load_state_dict`` (the `core.`
-    sub-dict PatchFusion._load_branch hands to providers, or MiDaS names directly); loading is strict.  Float32 only; the block linears
-    follow PF_LINEAR_SPLIT3 (=0 is refused: the f32 kernel route is not built for this core)."""
+    sub-dict PatchFusion._load_branch hands to providers, or MiDaS names directly); loading is strict.  In float32 the block linears
+    follow PF_LINEAR_SPLIT3 (=0 is refused: the f32 kernel route is not built for this core); in bfloat16 that switch is not consulted.
+    The packed weights are cached for ONE (device, dtype) at a time: a forward in the other dtype repacks (PatchFusion.set_compute_dtype)."""
 
     def __init__(self, settings="DPT_BEiT_L_384", device=None, ops=None):
         self.s = dict(MIDAS_BEIT_SETTINGS[settings]) if isinstance(settings, str) else dict(settings)
@@ -70,6 +77,7 @@ class MidasBeitCore:
         self._ops = ops
         self._packed = None
         self._sd = None
+        self.call_dtype = F32                    # compute dtype of the NCHW provider protocol (__call__); its results are float32 either way
 
     # ------------------------------------------------------------------ loading
     def load_state_dict(self, sd, strict=True):
@@ -89,28 +97,37 @@ class MidasBeitCore:
         self._packed = None
         return self
 
-    def _pack(self, device, ops):
+    def forget_packed(self):
+        """drop the packed weights (they are rebuilt, for the dtype then asked for, at the next forward)"""
+        self._packed = None
+
+    def _pack(self, device, ops, dtype=F32):
         s, sd = self.s, self._sd
         if sd is None:
             raise RuntimeError("MidasBeitCore has no weights: load_state_dict() first")
-        if not (getattr(ops, "conv_split3", None) is not None and _linear_split3_enabled()):
+        if dtype not in (F32, BF16):
+            raise NotImplementedError(f"MidasBeitCore computes in float32 or bfloat16, not {dtype}")
+        if dtype == F32 and not (getattr(ops, "conv_split3", None) is not None and _linear_split3_enabled()):
             raise NotImplementedError("MidasBeitCore runs its block linears as split-precision GEMMs only (PF_LINEAR_SPLIT3=0 is not built)")
         H, W = s["img_size"]
         th, tw, D = H // 16, W // 16, s["D"]
 
         def pc(name, bias=True, **kw):
-            return pk.pack_conv(sd[name + ".weight"], sd[name + ".bias"] if bias else None, dtype=F32, **kw).to(device)
+            return pk.pack_conv(sd[name + ".weight"], sd[name + ".bias"] if bias else None, dtype=dtype, **kw).to(device)
 
         m = "pretrained.model."
         w = sd[m + "patch_embed.proj.weight"]
         P = dict(th=th, tw=tw)
-        P["pe"] = pk.pack_conv(w.permute(0, 2, 3, 1).reshape(D, -1), sd[m + "patch_embed.proj.bias"], dtype=F32).to(device)
+        P["pe"] = pk.pack_conv(w.permute(0, 2, 3, 1).reshape(D, -1), sd[m + "patch_embed.proj.bias"], dtype=dtype).to(device)
         P["cls"] = sd[m + "cls_token"].reshape(-1).to(device)
         P["zpos"] = torch.zeros((th * tw + 1) * D, dtype=F32, device=device)          # BEiT-L has no absolute position embedding
         blocks = []
         for i in range(s["depth"]):
             b = f"{m}blocks.{i}."
             qb = torch.cat([sd[b + "attn.q_bias"], torch.zeros_like(sd[b + "attn.v_bias"]), sd[b + "attn.v_bias"]])   # k has no bias
+            if dtype == BF16:
+                blocks.append(pk.pack_beit_block_bf16(sd, b, qb, s["pretrain"], th, tw).to(device))
+                continue
             blocks.append(dict(
                 n1=(sd[b + "norm1.weight"].to(device), sd[b + "norm1.bias"].to(device)),
                 qkv=pk.pack_conv_split3(sd[b + "attn.qkv.weight"], qb).to(device),
@@ -125,7 +142,7 @@ class MidasBeitCore:
             p = f"pretrained.act_postprocess{i + 1}."
             e = dict(readout=pc(p + "0.project.0"), conv=pc(p + "3"))
             if i in (0, 1):
-                e["post"] = pk.pack_conv_transpose(sd[p + "4.weight"], sd[p + "4.bias"], dtype=F32).to(device)
+                e["post"] = pk.pack_conv_transpose(sd[p + "4.weight"], sd[p + "4.bias"], dtype=dtype).to(device)
             elif i == 3:
                 e["post"] = pc(p + "4")
             pp.append(e)
@@ -138,7 +155,7 @@ class MidasBeitCore:
                                   u1=None if i == 4 else (pc(r + "resConfUnit1.conv1"), pc(r + "resConfUnit1.conv2")))
         P["oc0"], P["oc2"], P["oc4"] = pc("scratch.output_conv.0"), pc("scratch.output_conv.2"), pc("scratch.output_conv.4")
         P["oc4"].cout = 8        # widen the 1-channel conv to 8 stored channels (zero rows / bias, ReLU -> zeros): fills a clb tail in one store
-        P["device"] = device
+        P["device"], P["dtype"] = device, dtype
         self._packed = P
         return P
 
@@ -153,14 +170,14 @@ class MidasBeitCore:
         dev = self.device or img.device
         ops = self._ops_for(dev)
         img = img.to(device=dev, dtype=F32)
-        rel, feats = self.forward_nhwc(ops, img)
-        return rel[..., 0].contiguous(), [f.permute(0, 3, 1, 2).contiguous() for f in feats]
+        rel, feats = self.forward_nhwc(ops, img, dtype=self.call_dtype)
+        return rel[..., 0].float().contiguous(), [f.permute(0, 3, 1, 2).float().contiguous() for f in feats]
 
     def _rcu(self, ops, x, unit, extra_res=None):
         c1, c2 = unit
-        t = ops.empty(x.shape[:3] + (c1.cout,), F32, x.device)
+        t = ops.empty(x.shape[:3] + (c1.cout,), x.dtype, x.device)
         ops.conv(x, c1, t, pad=1, act="relu", relu_in=True)
-        y = ops.empty(x.shape[:3] + (c2.cout,), F32, x.device)
+        y = ops.empty(x.shape[:3] + (c2.cout,), x.dtype, x.device)
         ops.conv(t, c2, y, pad=1, res=x, res2=extra_res)
         return y
 
@@ -170,21 +187,36 @@ class MidasBeitCore:
             x = self._rcu(ops, skip, r["u1"], extra_res=x)
         x = self._rcu(ops, x, r["u2"])
         B, _, _, Cc = x.shape
-        u = ops.empty((B, size[0], size[1], Cc), F32, x.device)
+        u = ops.empty((B, size[0], size[1], Cc), x.dtype, x.device)
         ops.resize(x, u)
-        y = ops.empty((B, size[0], size[1], r["out"].cout), F32, x.device)
+        y = ops.empty((B, size[0], size[1], r["out"].cout), x.dtype, x.device)
         ops.conv(u, r["out"], y)
         return y
 
-    def forward_nhwc(self, ops, img, out_conv=None, rel=None):
+    def _hook(self, ops, P, i, x, rc, hooked, B, S, dt):
+        th, tw, D = P["th"], P["tw"], self.s["D"]
+        for k, hb in enumerate(self.s["hooks"]):                       # hooks: the block outputs themselves (no final LayerNorm)
+            if hb == i:
+                ops.readout_concat(x, rc, B, S)
+                f = ops.empty((B, th, tw, D), dt, x.device)
+                ops.conv(rc, P["pp"][k]["readout"], f.view(B * th * tw, D), act="gelu")
+                hooked[k] = f
+
+    def forward_nhwc(self, ops, img, out_conv=None, rel=None, dtype=None):
         """img float32 [B,3,H,W] in [0,1] on the GPU -> (rel [B,H,W,8] (channel 0 = rel_depth, 1..7 zero), [l4_rn, r4, r3, r2, r1, out_conv]
-        NHWC float32).  ``out_conv`` / ``rel``: NHWC views [B,H,W,32] / [B,H,W,8] to write those two maps into (the branch's clb buffer)."""
+        NHWC in ``dtype`` (float32 by default, or bfloat16).  ``out_conv`` / ``rel``: NHWC views [B,H,W,32] / [B,H,W,8] of that dtype to write
+        those two maps into (the branch's clb buffer)."""
         dev = img.device
-        P = self._packed if self._packed is not None and self._packed["device"] == dev else self._pack(dev, ops)
+        dt = F32 if dtype is None else dtype
+        P = self._packed
+        if P is None or P["device"] != dev or P["dtype"] != dt:
+            P = self._pack(dev, ops, dt)
         s = self.s
         H, W = s["img_size"]
         B = img.shape[0]
         for buf, C in ((out_conv, 32), (rel, 8)):
+            if buf is not None and buf.dtype != dt:
+                raise ValueError(f"MidasBeitCore.forward_nhwc: output buffer is {buf.dtype}, the core computes in {dt}")
             if buf is not None and tuple(buf.shape) != (B, H, W, C):
                 raise ValueError(f"MidasBeitCore.forward_nhwc: output buffer {tuple(buf.shape)} does not match img_size {(H, W)} (B = {B}, {C} channels)")
         if tuple(img.shape[2:]) != (H, W):              # PrepForMidas's resize (midas.py:171-173): bilinear, align_corners=True
@@ -197,21 +229,34 @@ class MidasBeitCore:
         img = img.contiguous()
         th, tw, D, heads = P["th"], P["tw"], s["D"], s["heads"]
         T, S = th * tw, th * tw + 1
-        col = ops.empty((B * T, 768), F32, dev)
+        col = ops.empty((B * T, 768), dt, dev)
         ops.patch_im2col_norm(img, col, 16, (0.5, 0.5, 0.5), (0.5, 0.5, 0.5))
-        emb = ops.empty((B * T, D), F32, dev)
+        emb = ops.empty((B * T, D), dt, dev)
         ops.conv(col, P["pe"], emb)
-        tok = ops.empty((B, S, D), F32, dev)
+        tok = ops.empty((B, S, D), dt, dev)
         ops.assemble_tokens(emb, tok, P["cls"], P["zpos"])
         x = tok.view(B * S, D)
-        if pk.split3_kmajor_enabled():
+        if dt == BF16:                                   # plain bf16 rows, as BranchNet.vit's bf16 route
+            hbuf, att, mid, qkv = (ops.empty((B * S, n), dt, dev) for n in (D, D, 4 * D, 3 * D))
+        elif pk.split3_kmajor_enabled():
             hbuf, att, mid = (ops.empty((3, n // 32, B * S, 32), torch.bfloat16, dev) for n in (D, D, 4 * D))
         else:
             hbuf, att, mid = (ops.empty((3, B * S, n), torch.bfloat16, dev) for n in (D, D, 4 * D))
-        qkv = ops.empty((3, B * S, 3 * D), torch.bfloat16, dev)
-        rc = ops.empty((B * T, 2 * D), F32, dev)
+        if dt == F32:
+            qkv = ops.empty((3, B * S, 3 * D), torch.bfloat16, dev)
+        rc = ops.empty((B * T, 2 * D), dt, dev)
         hooked = [None] * 4
         for i, blk in enumerate(P["blocks"]):
+            if dt == BF16:
+                ops.layernorm(x, hbuf, blk.n1[0], blk.n1[1], 1e-6)
+                ops.conv(hbuf, blk.qkv, qkv)
+                ops.vit_attention_rpb_bf16(qkv, att, B, S, heads, blk.tab, th, tw)
+                ops.conv(att, blk.proj, x, res=x)                       # x += gamma_1 * proj(attn): gamma folded into the packed weight
+                ops.layernorm(x, hbuf, blk.n2[0], blk.n2[1], 1e-6)
+                ops.conv(hbuf, blk.fc1, mid, act="gelu")
+                ops.conv(mid, blk.fc2, x, res=x)                        # x += gamma_2 * fc2(gelu(fc1))
+                self._hook(ops, P, i, x, rc, hooked, B, S, dt)
+                continue
             ops.layernorm_split3(x, hbuf, blk["n1"][0], blk["n1"][1], 1e-6)
             ops.conv_split3(hbuf, blk["qkv"], qkv)
             ops.vit_attention_rpb(qkv, att, B, S, heads, blk["tab"], th, tw)
@@ -219,32 +264,27 @@ class MidasBeitCore:
             ops.layernorm_split3(x, hbuf, blk["n2"][0], blk["n2"][1], 1e-6)
             ops.conv_split3(hbuf, blk["fc1"], mid, act="gelu")
             ops.conv_split3(mid, blk["fc2"], x, res=x)                  # x += gamma_2 * fc2(gelu(fc1))
-            for k, hb in enumerate(s["hooks"]):                        # hooks: the block outputs themselves (no final LayerNorm)
-                if hb == i:
-                    ops.readout_concat(x, rc, B, S)
-                    f = ops.empty((B, th, tw, D), F32, dev)
-                    ops.conv(rc, P["pp"][k]["readout"], f.view(B * T, D), act="gelu")
-                    hooked[k] = f
+            self._hook(ops, P, i, x, rc, hooked, B, S, dt)
         maps = []
         for k, f in enumerate(hooked):
             e = P["pp"][k]
-            p = ops.empty((B, th, tw, e["conv"].cout), F32, dev)
+            p = ops.empty((B, th, tw, e["conv"].cout), dt, dev)
             ops.conv(f, e["conv"], p)
             if k == 0:
-                y = ops.empty((B, th * 4, tw * 4, e["conv"].cout), F32, dev)
+                y = ops.empty((B, th * 4, tw * 4, e["conv"].cout), dt, dev)
                 ops.conv(p, e["post"], y)
             elif k == 1:
-                y = ops.empty((B, th * 2, tw * 2, e["conv"].cout), F32, dev)
+                y = ops.empty((B, th * 2, tw * 2, e["conv"].cout), dt, dev)
                 ops.conv(p, e["post"], y)
             elif k == 2:
                 y = p
             else:
-                y = ops.empty((B, (th + 1) // 2, (tw + 1) // 2, e["conv"].cout), F32, dev)
+                y = ops.empty((B, (th + 1) // 2, (tw + 1) // 2, e["conv"].cout), dt, dev)
                 ops.conv(p, e["post"], y, stride=2, pad=1)
             maps.append(y)
         rn = []
         for k in range(4):
-            y = ops.empty(maps[k].shape[:3] + (P["rn"][k].cout,), F32, dev)
+            y = ops.empty(maps[k].shape[:3] + (P["rn"][k].cout,), dt, dev)
             ops.conv(maps[k], P["rn"][k], y, pad=1)
             rn.append(y)
         R = P["refine"]
@@ -252,15 +292,15 @@ class MidasBeitCore:
         r3 = self._refine(ops, R[3], r4, rn[2], rn[1].shape[1:3])
         r2 = self._refine(ops, R[2], r3, rn[1], rn[0].shape[1:3])
         r1 = self._refine(ops, R[1], r2, rn[0], (rn[0].shape[1] * 2, rn[0].shape[2] * 2))
-        o0 = ops.empty(r1.shape[:3] + (P["oc0"].cout,), F32, dev)
+        o0 = ops.empty(r1.shape[:3] + (P["oc0"].cout,), dt, dev)
         ops.conv(r1, P["oc0"], o0, pad=1)
-        o0u = ops.empty((B, H, W, P["oc0"].cout), F32, dev)
+        o0u = ops.empty((B, H, W, P["oc0"].cout), dt, dev)
         ops.resize(o0, o0u)
         if out_conv is None:
-            out_conv = ops.empty((B, H, W, 32), F32, dev)
+            out_conv = ops.empty((B, H, W, 32), dt, dev)
         ops.conv(o0u, P["oc2"], out_conv, pad=1, act="relu")          # hooked 'out_conv' (output_conv child 3)
         if rel is None:
-            rel = ops.empty((B, H, W, 8), F32, dev)
+            rel = ops.empty((B, H, W, 8), dt, dev)
         ops.conv(out_conv, P["oc4"], rel, act="relu")
         return rel, [rn[3], r4, r3, r2, r1, out_conv]
 

@@ -339,6 +339,9 @@ class PatchFusion(nn.Module, PyTorchModelHubMixin):
     def set_compute_dtype(self, dtype):
         self.compute_dtype = _DTYPES[dtype]
         self._engine = None
+        for p in tuple(getattr(self, "core_providers", ())) + (getattr(self, "core_provider", None),):
+            if hasattr(p, "forget_packed"):                       # a native core repacks its weights for the new dtype at its next forward
+                p.forget_packed()
 
     # ------------------------------------------------------------------ engine
     @property

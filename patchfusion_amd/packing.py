@@ -495,3 +495,46 @@ def beit_rel_pos_table(table, pretrain, th, tw):
     new = new.permute(0, 2, 3, 1).reshape((2 * th - 1) * (2 * tw - 1), -1)
     full = torch.cat([new, t[old * old:]])
     return (full * math.log2(math.e)).t().contiguous()
+
+
+@dataclass
+class BeitBlockBF16:
+    """One BEiT block of the MiDaS core packed for the bf16 mode (midas_core.MidasBeitCore, compute_dtype="bf16")"""
+    n1: tuple                       # (weight, bias) float32
+    qkv: PackedConv                 # bfloat16, bias [q_bias, 0, v_bias] float32
+    tab: torch.Tensor               # float32 [heads, (2 th - 1)(2 tw - 1) + 3], times log2(e)  (beit_rel_pos_table)
+    proj: PackedConv                # bfloat16, gamma_1 folded
+    n2: tuple
+    fc1: PackedConv
+    fc2: PackedConv                 # bfloat16, gamma_2 folded
+
+    def to(self, device):
+        self.n1 = tuple(t.to(device) for t in self.n1)
+        self.n2 = tuple(t.to(device) for t in self.n2)
+        self.tab = self.tab.to(device)
+        for pc in (self.qkv, self.proj, self.fc1, self.fc2):
+            pc.to(device)
+        return self
+
+
+def fold_layer_scale(weight, bias, gamma):
+    """LayerScale folded into a linear layer: gamma * (W x + b) = (gamma W) x + gamma b, the products taken in float64 and rounded once"""
+    g = gamma.detach().double().cpu()
+    return (g[:, None] * weight.detach().double().cpu()).float(), (g * bias.detach().double().cpu()).float()
+
+
+def pack_beit_block_bf16(sd, b, qkv_bias, pretrain, th, tw):
+    """The four linears of BEiT block ``b`` (a key prefix of ``sd``) as plain bfloat16 pack_conv layers -- what the Depth-Anything bf16 branch
+    uses -- with BEiT's additions: the qkv bias [q_bias, 0, v_bias] (k has none), gamma_1 / gamma_2 folded into proj / fc2 (bfloat16 holds
+    round-to-nearest-even of gamma * W, the float32 bias gamma * b), and the layer's relative-position table."""
+    bf = torch.bfloat16
+    pw, pb = fold_layer_scale(sd[b + "attn.proj.weight"], sd[b + "attn.proj.bias"], sd[b + "gamma_1"])
+    fw, fb = fold_layer_scale(sd[b + "mlp.fc2.weight"], sd[b + "mlp.fc2.bias"], sd[b + "gamma_2"])
+    return BeitBlockBF16(
+        n1=(sd[b + "norm1.weight"].detach().float(), sd[b + "norm1.bias"].detach().float()),
+        qkv=pack_conv(sd[b + "attn.qkv.weight"], qkv_bias, dtype=bf),
+        tab=beit_rel_pos_table(sd[b + "attn.relative_position_bias_table"], pretrain, th, tw),
+        proj=pack_conv(pw, pb, dtype=bf),
+        n2=(sd[b + "norm2.weight"].detach().float(), sd[b + "norm2.bias"].detach().float()),
+        fc1=pack_conv(sd[b + "mlp.fc1.weight"], sd[b + "mlp.fc1.bias"], dtype=bf),
+        fc2=pack_conv(fw, fb, dtype=bf))
