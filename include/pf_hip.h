@@ -89,15 +89,31 @@ int pf_conv_winograd_split3_windowed(const pf_conv_params* p, const void* U3, in
  * scale, three f16 MFMAs per product instead of six bf16 ones.  U = PackedConv.wino_u, float32 [36][u_rows][Cin] (u_kpad == Cin, u_rows % 16 == 0);
  * V2 = arena of 2 x 36 x window x Cin fp16 (window % 8 == 0, 0 = all tiles), M = 36 x window x Cout float32, scratch = pf_wino_f16x2_scratch_bytes
  * bytes (per-call channel maxima of x, the scaled filter planes and their column exponents).  Same argument rules as the bf16x3 entry, the x / y alias
- * refusal included.  pf_conv_winograd_f16x2_supported returns 1 when a call qualifies and its product runs on the 192 x 192 kernel (the only tile
- * with an fp16x2 form), else 0 -- the caller then takes pf_conv_winograd_split3_windowed. */
+ * refusal included.  pf_conv_winograd_f16x2_supported returns 1 when a call qualifies and the product of the whole layer has an fp16x2 kernel
+ * (pf_gemm_f16x2_points_route >= 0: the persistent 192 x 192 or 128 x 128 walk), else 0 -- the caller then takes pf_conv_winograd_split3_windowed. */
 long pf_wino_f16x2_scratch_bytes(int cin, int u_rows);
 int pf_conv_winograd_f16x2_supported(const pf_conv_params* p, int u_rows, int u_kpad, long window);
 int pf_conv_winograd_f16x2_windowed(const pf_conv_params* p, const void* U, int u_rows, int u_kpad, void* V2, void* M, void* scratch, long window,
                                     void* stream);
+/* the same call with the range pass handed from layer to layer: cmax_in = the channel maxima of x (uint32 [Cin] float bits, of relu(x) when
+ * p->relu_in) as the producer's output transform merged them, or NULL = run the range pass; cmax_out = NULL or a uint32 [Cout] buffer into which this
+ * layer's output transform merges max |y| per channel (of max(y, 0) when cmax_out_relu != 0); it is zeroed once per call, every window accumulates
+ * into it, and it equals what the range pass computes on y bit for bit.  y is bit-identical with and without cmax_out. */
+int pf_conv_winograd_f16x2_windowed_ex(const pf_conv_params* p, const void* U, int u_rows, int u_kpad, void* V2, void* M, void* scratch, long window,
+                                       const void* cmax_in, void* cmax_out, int cmax_out_relu, void* stream);
+/* pf_conv_winograd_split3_windowed as such a producer */
+int pf_conv_winograd_split3_windowed_ex(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, void* V3, void* M, long window, void* cmax_out,
+                                        int cmax_out_relu, void* stream);
+/* the range pass alone (the reference of the hand-over): cmax uint32 [C] must be zeroed by the caller; x float32 [P][x_ld], C % 4 == 0 */
+int pf_wino_absmax(const void* x, int x_ld, long P, int C, int relu_in, void* cmax, void* stream);
 /* its batched product alone: x / w = two fp16 planes each, chunk-major (korder = 6, batch = transform points, no epilogue), y float32 =
  * ldexp(sum, col_exp[z][n]) with col_exp int32 [batch][w_rows] */
 int pf_gemm_f16x2_points(const pf_conv_params* p, const int* col_exp, int grid_cap, void* stream);
+/* the same product on 128 x 128 tiles (csrc/wino_f16x2_n256.hip; the 256-column layers): same operands, same result bits */
+int pf_gemm_f16x2_points128(const pf_conv_params* p, const int* col_exp, int grid_cap, void* stream);
+/* which of the two runs the product of a whole layer on a chip of `cus` compute units: PF_S3_ROUTE_PERSIST192, PF_S3_ROUTE_PERSIST128, or -1 when
+ * the layer stays on three bf16 planes (pf_gemm_split3_route gives TILE64 / TILE128, or PF_WINO_F16X2_N256=0 for the 128-tile layers, or a 128-tile layer outside the measured rule -- K >= 512 and >= 4096 tiles; =3: every one); no launch */
+int pf_gemm_f16x2_points_route(const pf_conv_params* p, int cus);
 /* fp16x2 linear layer (the ViT block linears; packing.pack_conv_f16x2): x = two fp16 planes, chunk-major [2][K/32][M][32], holding x / 2^e_k;
  * w = two fp16 planes [2][K/32][w_rows][32] holding W[n][k] 2^(e_k - f_n); korder must be 6 (| 16, see below).  p->col_exp = f_n [w_rows] (required).
  * The persistent 192 x 192 kernel sums the three products hh, hl, lh in float32, applies ldexp(acc, f_n) and then the pf_conv epilogue

@@ -59,7 +59,11 @@ SIGNATURES = {
     "pf_conv_winograd_split3": [C.POINTER(ConvParams), vp, ci, ci, vp, vp, vp],
     "pf_conv_winograd_split3_windowed": [C.POINTER(ConvParams), vp, ci, ci, vp, vp, C.c_long, vp],
     "pf_conv_winograd_f16x2_windowed": [C.POINTER(ConvParams), vp, ci, ci, vp, vp, vp, C.c_long, vp],
+    "pf_conv_winograd_f16x2_windowed_ex": [C.POINTER(ConvParams), vp, ci, ci, vp, vp, vp, C.c_long, vp, vp, ci, vp],
+    "pf_conv_winograd_split3_windowed_ex": [C.POINTER(ConvParams), vp, ci, ci, vp, vp, C.c_long, vp, ci, vp],
+    "pf_wino_absmax": [vp, ci, cl, ci, ci, vp, vp],
     "pf_gemm_f16x2_points": [C.POINTER(ConvParams), vp, ci, vp],
+    "pf_gemm_f16x2_points128": [C.POINTER(ConvParams), vp, ci, vp],
     "pf_gemm_f16x2": [C.POINTER(ConvParams), vp],
     "pf_gemm_split3": [C.POINTER(ConvParams), vp],
     "pf_gemm_split3_ex": [C.POINTER(ConvParams), ci, vp],
@@ -100,6 +104,7 @@ SIGNATURES = {
     "pf_depth_metrics": [vp, ci, ci, vp, ci, ci, vp, vp, cf, cf, ci, ci, ci, ci, vp, vp],
 }
 NON_STATUS = ("pf_last_error", "pf_version", "pf_percentile_workspace_bytes", "pf_conv_winograd_fused_supported", "pf_gemm_split3_route",
+              "pf_gemm_f16x2_points_route",
               "pf_wino_f16x2_scratch_bytes", "pf_conv_winograd_f16x2_supported", "pf_vit_attention_rpb_bf16_lds_bytes")   # entry points that do not return a status
 
 _lib = None
@@ -129,6 +134,8 @@ def load():
     lib.pf_conv_winograd_fused_supported.argtypes = [C.POINTER(ConvParams)]
     lib.pf_gemm_split3_route.restype = ci                      # PF_S3_ROUTE_* (or -1), not a status
     lib.pf_gemm_split3_route.argtypes = [C.POINTER(ConvParams), ci]
+    lib.pf_gemm_f16x2_points_route.restype = ci                # PF_S3_ROUTE_PERSIST192 / PERSIST128 (or -1), not a status
+    lib.pf_gemm_f16x2_points_route.argtypes = [C.POINTER(ConvParams), ci]
     lib.pf_wino_f16x2_scratch_bytes.restype = C.c_long                 # bytes, not a status
     lib.pf_wino_f16x2_scratch_bytes.argtypes = [ci, ci]
     lib.pf_conv_winograd_f16x2_supported.restype = ci                 # 1 / 0, not a status

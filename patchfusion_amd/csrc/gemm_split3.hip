@@ -1301,11 +1301,37 @@ int split3_route(const pf_conv_params& p, int cus) {
   return PF_S3_ROUTE_TILE128;
 }
 
+// Which fp16x2 kernel runs the batched transform-domain product of a three-step Winograd layer (p = the product of the WHOLE layer), or -1 when the
+// layer stays on three bf16 planes -- the whole rule in one place (pf_gemm_f16x2_points_route exposes it to the CPU tests):
+//   PERSIST192  the bf16x3 product would walk 192 x 192 tiles: their F16 form (round 7)
+//   PERSIST128  the bf16x3 product would walk 128 x 128 tiles (the 256-column layers): gemm_f16x2_persist128_kernel, csrc/wino_f16x2_n256.hip,
+//               where the LAYER measured faster (profiles/r11_n256_sweep.md): K >= 512 and at least 4096 Winograd tiles.  The product itself gains
+//               1.19-1.26x at K >= 512 but 1.02-1.07x at K = 256 (cause not measured: no counter run; nominal V + M bytes over the time give 3.2 TB/s); the fp16x2 layer also pays the per-call range pass and U' split (three more launches), which 2128 tiles do not earn back
+//               (512->256 @ 8x56x74: 0.85x).  The thresholds are fitted to the shapes of the pass: nothing was timed between 2128 and 8288
+//               tiles nor at a K between 256 and 512.  PF_WINO_F16X2_N256 (A/B, read per call): 0 keeps these layers on the bf16x3 planes,
+//               1 and 2 = this rule (2: hip_ops keeps the range pass instead of the producer's maxima), 3 = every PERSIST128 layer.
+//   -1          TILE64 / TILE128: fewer than two rounds of tiles, where a persistent fp16x2 walk measured 0.36-0.93x (round 8)
+int f16x2_points_route(const pf_conv_params& p, int cus) {
+  const int r = split3_route(p, cus);
+  if (r == PF_S3_ROUTE_PERSIST192) return r;
+  if (r != PF_S3_ROUTE_PERSIST128) return -1;
+  const char* s = getenv("PF_WINO_F16X2_N256");
+  const char mode = s ? s[0] : '1';
+  if (mode == '0') return -1;
+  if (mode == '3') return r;
+  return p.Cin >= 512 && (long)p.B * p.OH * p.OW >= 4096 ? r : -1;
+}
+
 }  // namespace
 
 extern "C" int pf_gemm_split3_route(const pf_conv_params* p, int cus) {
   if (!p || cus <= 0) return -1;
   return split3_route(*p, cus);
+}
+
+extern "C" int pf_gemm_f16x2_points_route(const pf_conv_params* p, int cus) {
+  if (!p || cus <= 0) return -1;
+  return f16x2_points_route(*p, cus);
 }
 
 namespace {

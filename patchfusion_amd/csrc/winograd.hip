@@ -21,6 +21,7 @@ int launch_absmax(const float* x, int x_ld, long P, int C, int relu_in, unsigned
 int launch_u_split(const float* U, int rows, int C, const unsigned* cmax, void* U2, int* fexp, hipStream_t st);
 int launch_input(const float* x, int x_ld, int B, int H, int W, int C, int relu_in, const unsigned* cmax, void* V, int TH, int TW, long tile0, long T,
                  hipStream_t st);
+int launch_output_cmax(const float* M, const pf_conv_params* p, int TH, int TW, long t0, long T, unsigned* cmax, int cmax_relu, hipStream_t st);
 }  // namespace pf_f16x2
 
 namespace {
@@ -293,7 +294,10 @@ bool windows_alias(const pf_conv_params* p) {
 
 // F(4x4,3x3) with the transform-domain GEMM in split precision: V is written as three bf16 planes, U3 = the three planes of G g G^T
 // (chunk-major [3][36][Cin/32][u_rows][32] bf16 = PackedConv.wino_u3, the split3 of packing.winograd_filters), ONE batched pf_gemm_split3 launch (plane = blockIdx.y), M float32.
-int run_split3(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, void* V3, float* M, long window, hipStream_t st) {
+// cmax_out != nullptr: the output transform also merges the channel maxima of y (of max(y, 0) with cmax_relu) into that uint32 [Cout] buffer, zeroed
+// here once before the first window -- the range pass of a following fp16x2 layer (csrc/wino_f16x2_n256.hip wino_output_cmax_kernel).
+int run_split3(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, void* V3, float* M, long window, hipStream_t st,
+               unsigned* cmax_out = nullptr, int cmax_relu = 0) {
   constexpr int MT = 4, A = 6;
   const int TH = (p->H + MT - 1) / MT, TW = (p->W + MT - 1) / MT;
   const long Tall = (long)p->B * TH * TW;
@@ -308,6 +312,7 @@ int run_split3(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, 
   hipEvent_t tok = sw.token ? gemm_token() : nullptr;
   // (x and y of a layer in several windows must not share an element: windows_alias.)  Refused instead of computing from half-overwritten input.
   if (window < Tall && windows_alias(p)) return PF_ERR_ARG;
+  if (cmax_out && hipMemsetAsync(cmax_out, 0, (size_t)p->Cout * 4, st) != hipSuccess) return PF_ERR_LAUNCH;
   // TILE WINDOWS (round 5): the layer's tiles go through the three steps `window` tiles at a time, all windows through the SAME V / M arena -- launches
   // of one stream are ordered.  Winograd tiles are independent, so the numbers do not depend on the window.
   for (long t0 = 0; t0 < Tall; t0 += window) {
@@ -333,17 +338,22 @@ int run_split3(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, 
     if (rc != PF_OK) return rc;
     if (tok) hipEventRecord(tok, st);
     const bool resident_out = tgrid > 0 && nout > (long)tgrid * 512 * 4;
+    if (cmax_out) {
+      const int rc2 = pf_f16x2::launch_output_cmax(M, p, TH, TW, t0, T, cmax_out, cmax_relu, st);
+      if (rc2 != PF_OK) return rc2;
+    } else
     hipLaunchKernelGGL(wino_output_kernel<MT>, resident_out ? dim3((unsigned)tgrid) : dim3((unsigned)((nout + 255) / 256)), resident_out ? dim3(512) : dim3(256), 0, st, M,
                        p->Cout, p->bias, p->act == PF_ACT_RELU ? 1 : 0, static_cast<const float*>(p->res), p->res_ld, static_cast<const float*>(p->res2),
                        p->res2_ld, static_cast<float*>(p->y), p->y_ld, p->B, p->H, p->W, TH, TW, t0, T);
-    if (launch_ok() != PF_OK) return PF_ERR_LAUNCH;
+    if (!cmax_out && launch_ok() != PF_OK) return PF_ERR_LAUNCH;
   }
   return PF_OK;
 }
 
 // fp16x2 form (round 7, csrc/wino_f16x2.hip): per layer call the channel maxima of the input and the scaled filter planes U' (scratch:
 // [2][36][Cin/32][u_rows][32] fp16 | int32 [36][u_rows] column exponents | uint32 [Cin] channel maxima), then per window the input transform into
-// two fp16 planes, the batched 192 x 192 product on three f16 MFMAs per term (pf_gemm_f16x2_points) and the output transform of run_split3.
+// two fp16 planes, the batched product on three f16 MFMAs per term (pf_gemm_f16x2_points on 192 x 192 tiles, pf_gemm_f16x2_points128 on 128 x 128
+// for the layers whose bf16x3 product walks 128-tiles: f16x2_layer_route) and the output transform of run_split3.
 // Same windows, same argument rules, one stream.
 struct F16x2Scratch { void* u2; int* fexp; unsigned* cmax; };
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -369,8 +379,24 @@ pf_conv_params f16x2_points_params(const pf_conv_params* p, const void* U2, int 
   return q;
 }
 
-int run_f16x2(const pf_conv_params* p, const float* U, int u_rows, void* V2, float* M, void* scratch, long window, hipStream_t st) {
+// The GEMM's tile is fixed by the product of the WHOLE layer (one window of all tiles), so every window size of a layer runs the same kernel.
+int f16x2_layer_route(const pf_conv_params* p, int u_rows) {
+  const long T = (long)p->B * ((p->H + 3) / 4) * ((p->W + 3) / 4);
+  if (T > 0x7fffffffL) return -1;
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  pf_conv_params q = f16x2_points_params(p, p->x, u_rows, const_cast<void*>(p->x), static_cast<float*>(p->y), T);
+  return pf_gemm_f16x2_points_route(&q, cus);
+}
+
+// cmax_in != nullptr: the channel maxima of x (uint32 [Cin], of relu(x) when relu_in) are already known -- handed over by the producer's output
+// transform -- and the memset + range pass are skipped.  cmax_out / cmax_relu: as run_split3.
+// A layer whose whole-layer route is -1 (called directly, or PF_WINO_F16X2_N256 flipped without a new plan) falls to the 192-tile product: correct
+// and the same bits, but not where that form was measured to win.
+int run_f16x2(const pf_conv_params* p, const float* U, int u_rows, void* V2, float* M, void* scratch, long window, hipStream_t st,
+              const unsigned* cmax_in = nullptr, unsigned* cmax_out = nullptr, int cmax_relu = 0) {
   constexpr int MT = 4;
+  const bool t128 = f16x2_layer_route(p, u_rows) == PF_S3_ROUTE_PERSIST128;
   const int TH = (p->H + MT - 1) / MT, TW = (p->W + MT - 1) / MT;
   const long Tall = (long)p->B * TH * TW;
   if (Tall > 0x7fffffffL) return PF_ERR_ARG;
@@ -378,19 +404,30 @@ int run_f16x2(const pf_conv_params* p, const float* U, int u_rows, void* V2, flo
   if (window < Tall && windows_alias(p)) return PF_ERR_ARG;   // (the alias rule of run_split3)
   const F16x2Scratch sc = f16x2_scratch(scratch, p->Cin, u_rows);
   const float* x = static_cast<const float*>(p->x);
-  if (hipMemsetAsync(sc.cmax, 0, (size_t)p->Cin * 4, st) != hipSuccess) return PF_ERR_LAUNCH;
-  int rc = pf_f16x2::launch_absmax(x, p->x_ld, (long)p->B * p->H * p->W, p->Cin, p->relu_in, sc.cmax, st);
-  if (rc != PF_OK) return rc;
-  rc = pf_f16x2::launch_u_split(U, u_rows, p->Cin, sc.cmax, sc.u2, sc.fexp, st);
+  int rc = PF_OK;
+  const unsigned* cmax = cmax_in;
+  if (!cmax) {
+    if (hipMemsetAsync(sc.cmax, 0, (size_t)p->Cin * 4, st) != hipSuccess) return PF_ERR_LAUNCH;
+    rc = pf_f16x2::launch_absmax(x, p->x_ld, (long)p->B * p->H * p->W, p->Cin, p->relu_in, sc.cmax, st);
+    if (rc != PF_OK) return rc;
+    cmax = sc.cmax;
+  }
+  if (cmax_out && hipMemsetAsync(cmax_out, 0, (size_t)p->Cout * 4, st) != hipSuccess) return PF_ERR_LAUNCH;
+  rc = pf_f16x2::launch_u_split(U, u_rows, p->Cin, cmax, sc.u2, sc.fexp, st);
   if (rc != PF_OK) return rc;
   for (long t0 = 0; t0 < Tall; t0 += window) {
     const long T = Tall - t0 < window ? Tall - t0 : window;
     const long nout = T * (p->Cout / 4);
-    rc = pf_f16x2::launch_input(x, p->x_ld, p->B, p->H, p->W, p->Cin, p->relu_in, sc.cmax, V2, TH, TW, t0, T, st);
+    rc = pf_f16x2::launch_input(x, p->x_ld, p->B, p->H, p->W, p->Cin, p->relu_in, cmax, V2, TH, TW, t0, T, st);
     if (rc != PF_OK) return rc;
     const pf_conv_params q = f16x2_points_params(p, sc.u2, u_rows, V2, M, T);
-    rc = pf_gemm_f16x2_points(&q, sc.fexp, 0, st);
+    rc = t128 ? pf_gemm_f16x2_points128(&q, sc.fexp, 0, st) : pf_gemm_f16x2_points(&q, sc.fexp, 0, st);
     if (rc != PF_OK) return rc;
+    if (cmax_out) {
+      rc = pf_f16x2::launch_output_cmax(M, p, TH, TW, t0, T, cmax_out, cmax_relu, st);
+      if (rc != PF_OK) return rc;
+      continue;
+    }
     hipLaunchKernelGGL(wino_output_kernel<MT>, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, M, p->Cout, p->bias, p->act == PF_ACT_RELU ? 1 : 0,
                        static_cast<const float*>(p->res), p->res_ld, static_cast<const float*>(p->res2), p->res2_ld, static_cast<float*>(p->y), p->y_ld,
                        p->B, p->H, p->W, TH, TW, t0, T);
@@ -415,23 +452,33 @@ extern "C" long pf_wino_f16x2_scratch_bytes(int cin, int u_rows) {
   return (long)(align256((size_t)2 * 36 * u_rows * cin * 2) + align256((size_t)36 * u_rows * 4) + align256((size_t)cin * 4));
 }
 
-// 1 when the layer runs the fp16x2 product: the arguments qualify and the bf16x3 GEMM of the WHOLE layer (all tiles in one window) would take the
-// persistent 192 x 192 kernel, the only one with an fp16x2 form (the N = 256 layers stay on 128 x 128 tiles and on the bf16x3 route).  The decision
-// does not depend on the window, so every window size of a layer computes the same bits.
+// 1 when the layer runs the fp16x2 product: the arguments qualify and the bf16x3 GEMM of the WHOLE layer (all tiles in one window) would take one
+// of the persistent kernels -- 192 x 192 tiles, or 128 x 128 (the N = 256 layers; csrc/wino_f16x2_n256.hip).  The rule is pf_gemm_f16x2_points_route
+// (csrc/gemm_split3.hip).  The decision does not depend on the window, so every window size of a layer computes the same bits.
 extern "C" int pf_conv_winograd_f16x2_supported(const pf_conv_params* p, int u_rows, int u_kpad, long window) {
   if (!f16x2_args_ok(p, u_rows, u_kpad, window)) return 0;
-  const long T = (long)p->B * ((p->H + 3) / 4) * ((p->W + 3) / 4);
-  if (T > 0x7fffffffL) return 0;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  pf_conv_params q = f16x2_points_params(p, p->x, u_rows, const_cast<void*>(p->x), static_cast<float*>(p->y), T);
-  return pf_gemm_split3_route(&q, cus) == PF_S3_ROUTE_PERSIST192 ? 1 : 0;
+  return f16x2_layer_route(p, u_rows) >= 0 ? 1 : 0;
 }
 
 extern "C" int pf_conv_winograd_f16x2_windowed(const pf_conv_params* p, const void* U, int u_rows, int u_kpad, void* V2, void* M, void* scratch,
                                                long window, void* stream) {
   if (!U || !V2 || !M || !scratch || !f16x2_args_ok(p, u_rows, u_kpad, window)) return PF_ERR_ARG;
   return run_f16x2(p, static_cast<const float*>(U), u_rows, V2, static_cast<float*>(M), scratch, window, ST(stream));
+}
+
+// the same call with the range pass handed between layers: cmax_in = the channel maxima of x as the producer's output transform merged them
+// (uint32 [Cin] float bits; of relu(x) when p->relu_in), or null = run the range pass; cmax_out = where this layer's output transform merges the
+// maxima of y (uint32 [Cout]; of max(y, 0) when cmax_out_relu), or null.  cmax_out must not be the buffer cmax_in points to.
+extern "C" int pf_conv_winograd_f16x2_windowed_ex(const pf_conv_params* p, const void* U, int u_rows, int u_kpad, void* V2, void* M, void* scratch,
+                                                  long window, const void* cmax_in, void* cmax_out, int cmax_out_relu, void* stream) {
+  if (!U || !V2 || !M || !scratch || !f16x2_args_ok(p, u_rows, u_kpad, window) || (cmax_in && cmax_in == cmax_out)) return PF_ERR_ARG;
+  return run_f16x2(p, static_cast<const float*>(U), u_rows, V2, static_cast<float*>(M), scratch, window, ST(stream),
+                   static_cast<const unsigned*>(cmax_in), static_cast<unsigned*>(cmax_out), cmax_out_relu);
+}
+
+extern "C" int pf_wino_absmax(const void* x, int x_ld, long P, int C, int relu_in, void* cmax, void* stream) {
+  if (!x || !cmax || P <= 0 || C <= 0 || C % 4 || x_ld < C || x_ld % 4) return PF_ERR_ARG;
+  return pf_f16x2::launch_absmax(static_cast<const float*>(x), x_ld, P, C, relu_in, static_cast<unsigned*>(cmax), ST(stream));
 }
 
 extern "C" int pf_conv_winograd_split3(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, void* V3, void* M, void* stream) {
@@ -452,6 +499,17 @@ extern "C" int pf_conv_winograd_split3_windowed(const pf_conv_params* p, const v
   if (p->act != PF_ACT_NONE && p->act != PF_ACT_RELU) return PF_ERR_ARG;
   if (u_rows < p->Cout || u_kpad != p->Cin) return PF_ERR_ARG;
   return run_split3(p, U3, u_rows, u_kpad, V3, static_cast<float*>(M), window, ST(stream));
+}
+
+// the same layer as the PRODUCER of an fp16x2 layer's range pass: its output transform merges the channel maxima of y into cmax_out (uint32 [Cout])
+extern "C" int pf_conv_winograd_split3_windowed_ex(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, void* V3, void* M, long window,
+                                                   void* cmax_out, int cmax_out_relu, void* stream) {
+  if (!p || !U3 || !V3 || !M || !p->x || !p->y || window < 0 || (window > 0 && window % 8)) return PF_ERR_ARG;
+  if (p->dtype != PF_DTYPE_F32 || p->KH != 3 || p->KW != 3 || p->stride != 1 || p->pad != 1 || p->shuffle > 1 || p->scale) return PF_ERR_ARG;
+  if (p->OH != p->H || p->OW != p->W || p->Cin % 32 || p->Cout % 8 || p->Cin <= 0 || p->Cout <= 0) return PF_ERR_ARG;
+  if (p->act != PF_ACT_NONE && p->act != PF_ACT_RELU) return PF_ERR_ARG;
+  if (u_rows < p->Cout || u_kpad != p->Cin) return PF_ERR_ARG;
+  return run_split3(p, U3, u_rows, u_kpad, V3, static_cast<float*>(M), window, ST(stream), static_cast<unsigned*>(cmax_out), cmax_out_relu);
 }
 
 extern "C" int pf_conv_winograd(const pf_conv_params* p, int m, const void* U, int u_rows, int u_kpad, void* V, void* M, void* stream) {

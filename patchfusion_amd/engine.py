@@ -280,8 +280,11 @@ class BranchNet:
         """x + conv2(relu(conv1(relu(x)))) [+ extra_res]  (blocks.py:69-92; ReLUs are non in-place)"""
         c1, c2 = unit
         t = ops.empty(x.shape[:3] + (c1.cout,), self.dtype, self.device)
-        ops.conv(x, c1, t, pad=1, act="relu", relu_in=True)
         y = ops.empty(x.shape[:3] + (c2.cout,), self.dtype, self.device)
+        chain = getattr(ops, "conv_chain", None)
+        if chain is not None:                                      # t is read by conv2 alone: conv1 hands over its channel maxima (hip_ops.conv_chain)
+            return chain(x, c1, t, c2, y, dict(pad=1, act="relu", relu_in=True), dict(pad=1, res=x, res2=extra_res))
+        ops.conv(x, c1, t, pad=1, act="relu", relu_in=True)
         ops.conv(t, c2, y, pad=1, res=x, res2=extra_res)
         return y
 

@@ -133,7 +133,9 @@ def _split3_three_step(pw):
 
 def _wino_f16x2_enabled():
     """three-step split layers whose product runs on the 192 x 192 kernel take its fp16x2 form (csrc/wino_f16x2.hip: two fp16 planes per operand with
-    power-of-two channel / column scales, three MFMAs per product instead of six); PF_WINO_F16X2=0 keeps every layer on the bf16x3 planes"""
+    power-of-two channel / column scales, three MFMAs per product instead of six), and so do the 128-tile layers the rule of
+    pf_gemm_f16x2_points_route picks (csrc/wino_f16x2_n256.hip; PF_WINO_F16X2_N256=0 / 2, read by the library); PF_WINO_F16X2=0 keeps every layer
+    on the bf16x3 planes"""
     return _env("PF_WINO_F16X2", "1") != "0"
 
 
@@ -196,12 +198,30 @@ def _f16x2_scratch(device, nbytes):
     return t
 
 
+_WSCMAX = {}
+
+
+def _cmax_buffer(device, n):
+    """per-(device, stream) uint32 buffer for the channel maxima a three-step layer hands to the fp16x2 layer that reads its output next (conv_chain)"""
+    key = (device.index, torch.cuda.current_stream().cuda_stream)
+    t = _WSCMAX.get(key)
+    if t is None or t.numel() < n:
+        t = _WSCMAX[key] = torch.empty(max(n, 1024), dtype=torch.int32, device=device)
+    return t
+
+
+def _cmax_handover_enabled():
+    """PF_WINO_F16X2_N256=2 (and 0): every fp16x2 layer runs its own range pass (A/B of the hand-over alone)"""
+    return _env("PF_WINO_F16X2_N256", "1") not in ("0", "2")
+
+
 def release_workspaces():
     """free the per-(device, stream) Winograd arenas (at the headline layer 12 GB + 8 GB per stream); they are re-grown on demand.  Also drops the
     cached dispatch plans: they hold strong references to the packed layers (device weights + Winograd filter planes, several GB for ViT-L), so
     `del model; release_workspaces(); torch.cuda.empty_cache()` really returns the memory (round-4 advisor finding)"""
     _WS.clear()
     _WS16.clear()
+    _WSCMAX.clear()
     _CONV_CACHE.clear()
 
 
@@ -313,7 +333,8 @@ class HipOps:
         return "direct", p, None          # (incl. fused-only layers below the block threshold)
 
     @staticmethod
-    def _conv_exec(route, p, extra, device):
+    def _conv_exec(route, p, extra, device, cmax_in=None, cmax_out=None, cmax_out_relu=False):
+        assert (cmax_in is None or route == "wino3h") and (cmax_out is None or route in ("wino3", "wino3h")), route
         if route == "direct":
             check(_L.pf_conv(C.byref(p), _stream()), "pf_conv")
         elif route == "s3_1x1":
@@ -322,11 +343,22 @@ class HipOps:
             check(_L.pf_conv_winograd_fused(C.byref(p), extra[0], extra[1], extra[2], _stream()), "pf_conv_winograd_fused")
         elif route == "wino3":
             V, Mw = _workspace(device, extra[3], extra[4])
+            if cmax_out is not None:
+                check(_L.pf_conv_winograd_split3_windowed_ex(C.byref(p), extra[0], extra[1], extra[2], C.c_void_p(V.data_ptr()), C.c_void_p(Mw.data_ptr()),
+                                                             extra[5], C.c_void_p(cmax_out.data_ptr()), int(cmax_out_relu), _stream()),
+                      "pf_conv_winograd_split3_windowed_ex")
+                return
             check(_L.pf_conv_winograd_split3_windowed(C.byref(p), extra[0], extra[1], extra[2], C.c_void_p(V.data_ptr()), C.c_void_p(Mw.data_ptr()),
                                                       extra[5], _stream()), "pf_conv_winograd_split3_windowed")
         elif route == "wino3h":
             V, Mw = _workspace(device, extra[3], extra[4])
             S = _f16x2_scratch(device, extra[6])
+            if cmax_in is not None or cmax_out is not None:
+                check(_L.pf_conv_winograd_f16x2_windowed_ex(C.byref(p), extra[0], extra[1], extra[2], C.c_void_p(V.data_ptr()), C.c_void_p(Mw.data_ptr()),
+                                                            C.c_void_p(S.data_ptr()), extra[5], None if cmax_in is None else C.c_void_p(cmax_in.data_ptr()),
+                                                            None if cmax_out is None else C.c_void_p(cmax_out.data_ptr()), int(cmax_out_relu), _stream()),
+                      "pf_conv_winograd_f16x2_windowed_ex")
+                return
             check(_L.pf_conv_winograd_f16x2_windowed(C.byref(p), extra[0], extra[1], extra[2], C.c_void_p(V.data_ptr()), C.c_void_p(Mw.data_ptr()),
                                                      C.c_void_p(S.data_ptr()), extra[5], _stream()), "pf_conv_winograd_f16x2_windowed")
         elif route == "wino":
@@ -342,25 +374,50 @@ class HipOps:
         The plan of a call -- checks, filled pf_conv_params, route -- is cached per (packed layer, tensor layouts, epilogue); a repeat call only
         refreshes the four data pointers (round-3 review: 22 us of Python per library call, most of it here)."""
         if _timed is None and _direct is None:
-            key = (id(pw), x.shape, x.stride(), y.shape, y.stride(), stride, pad, act, relu_in, x.dtype, y.dtype, x.device,
-                   None if res is None else (res.shape, res.stride(), res.dtype), None if res2 is None else (res2.shape, res2.stride(), res2.dtype),
-                   _align16(x, y, res, res2))
-            ent = _CONV_CACHE.get(key)
-            if ent is None or ent[0] is not pw:
-                if len(_CONV_CACHE) > 4096:
-                    _CONV_CACHE.clear()
-                ent = (pw,) + HipOps._conv_plan(x, pw, y, stride, pad, act, relu_in, res, res2, None)
-                _CONV_CACHE[key] = ent
-            else:
-                p = ent[2]
-                p.x, p.y = x.data_ptr(), y.data_ptr()
-                if res is not None:
-                    p.res = res.data_ptr()
-                if res2 is not None:
-                    p.res2 = res2.data_ptr()
+            ent = HipOps._conv_plan_cached(x, pw, y, stride, pad, act, relu_in, res, res2)
             HipOps._conv_exec(ent[1], ent[2], ent[3], x.device)
             return y
         route, p, extra = HipOps._conv_plan(x, pw, y, stride, pad, act, relu_in, res, res2, _direct)
+        return HipOps._conv_uncached(route, p, extra, x, y, _timed)
+
+    @staticmethod
+    def conv_chain(x, pw1, t, pw2, y, kw1, kw2):
+        """t = conv(x, pw1, **kw1); y = conv(t, pw2, **kw2) for a t that conv 2 reads whole and unmodified and nothing else writes (RCU conv1 -> conv2).
+        When conv 1 is a three-step Winograd layer and conv 2 an fp16x2 one, conv 1's output transform hands over the channel maxima of t and conv 2
+        skips its range pass (csrc/wino_f16x2_n256.hip wino_output_cmax_kernel; same bits either way); otherwise exactly two conv calls."""
+        e1 = HipOps._conv_plan_cached(x, pw1, t, kw1.get("stride", 1), kw1.get("pad", 0), kw1.get("act"), kw1.get("relu_in", False), kw1.get("res"), kw1.get("res2"))
+        e2 = HipOps._conv_plan_cached(t, pw2, y, kw2.get("stride", 1), kw2.get("pad", 0), kw2.get("act"), kw2.get("relu_in", False), kw2.get("res"), kw2.get("res2"))
+        if e1[1] in ("wino3", "wino3h") and e2[1] == "wino3h" and t.shape[-1] == pw1.cout == pw2.cin and _cmax_handover_enabled():
+            cm = _cmax_buffer(x.device, pw1.cout)
+            HipOps._conv_exec(e1[1], e1[2], e1[3], x.device, cmax_out=cm, cmax_out_relu=bool(kw2.get("relu_in", False)))
+            HipOps._conv_exec(e2[1], e2[2], e2[3], x.device, cmax_in=cm)
+        else:
+            HipOps._conv_exec(e1[1], e1[2], e1[3], x.device)
+            HipOps._conv_exec(e2[1], e2[2], e2[3], x.device)
+        return y
+
+    @staticmethod
+    def _conv_plan_cached(x, pw, y, stride, pad, act, relu_in, res, res2):
+        key = (id(pw), x.shape, x.stride(), y.shape, y.stride(), stride, pad, act, relu_in, x.dtype, y.dtype, x.device,
+               None if res is None else (res.shape, res.stride(), res.dtype), None if res2 is None else (res2.shape, res2.stride(), res2.dtype),
+               _align16(x, y, res, res2))
+        ent = _CONV_CACHE.get(key)
+        if ent is None or ent[0] is not pw:
+            if len(_CONV_CACHE) > 4096:
+                _CONV_CACHE.clear()
+            ent = (pw,) + HipOps._conv_plan(x, pw, y, stride, pad, act, relu_in, res, res2, None)
+            _CONV_CACHE[key] = ent
+        else:
+            p = ent[2]
+            p.x, p.y = x.data_ptr(), y.data_ptr()
+            if res is not None:
+                p.res = res.data_ptr()
+            if res2 is not None:
+                p.res2 = res2.data_ptr()
+        return ent
+
+    @staticmethod
+    def _conv_uncached(route, p, extra, x, y, _timed):
         if _timed is None:
             HipOps._conv_exec(route, p, extra, x.device)
             return y
