@@ -114,6 +114,12 @@ int pf_gemm_f16x2_points128(const pf_conv_params* p, const int* col_exp, int gri
 /* which of the two runs the product of a whole layer on a chip of `cus` compute units: PF_S3_ROUTE_PERSIST192, PF_S3_ROUTE_PERSIST128, or -1 when
  * the layer stays on three bf16 planes (pf_gemm_split3_route gives TILE64 / TILE128, or PF_WINO_F16X2_N256=0 for the 128-tile layers, or a 128-tile layer outside the measured rule -- K >= 512 and >= 4096 tiles; =3: every one); no launch */
 int pf_gemm_f16x2_points_route(const pf_conv_params* p, int cus);
+/* the same rule for a layer whose channel maxima are handed in (maxima_given != 0: no memset, no range pass).  At default switches the answer does not
+ * depend on maxima_given (the wider rule measured no gain in the image pass, profiles/r12_cmax_image_ab.md); under PF_WINO_F16X2_N256=5 the 128-tile
+ * layers with given maxima take fp16x2 from K >= 256 and 2128 Winograd tiles on (profiles/r11_n256_sweep.md, column "maxima given") */
+int pf_gemm_f16x2_points_route_ex(const pf_conv_params* p, int cus, int maxima_given);
+/* pf_conv_winograd_f16x2_supported by that rule, for a call that will pass cmax_in (maxima_given != 0) */
+int pf_conv_winograd_f16x2_supported_ex(const pf_conv_params* p, int u_rows, int u_kpad, long window, int maxima_given);
 /* fp16x2 linear layer (the ViT block linears; packing.pack_conv_f16x2): x = two fp16 planes, chunk-major [2][K/32][M][32], holding x / 2^e_k;
  * w = two fp16 planes [2][K/32][w_rows][32] holding W[n][k] 2^(e_k - f_n); korder must be 6 (| 16, see below).  p->col_exp = f_n [w_rows] (required).
  * The persistent 192 x 192 kernel sums the three products hh, hl, lh in float32, applies ldexp(acc, f_n) and then the pf_conv epilogue
@@ -299,6 +305,22 @@ int pf_maxpool2(const void* x, int x_ld, int B, int H, int W, int C, void* y, in
 /* channel-slice copy y[..., 0..C) = x[..., 0..C) with optional dtype change */
 int pf_copy_channels(const void* x, int x_ld, void* y, int y_ld, long npix, int C, int in_f32, int out_f32,
                      int dtype, void* stream);
+/* The same four calls as PRODUCERS of an fp16x2 Winograd layer's range pass (pf_conv_winograd_f16x2_windowed_ex cmax_in): with cmax != NULL (float32
+ * calls only, dtype == PF_DTYPE_F32, else PF_ERR_ARG) the kernel also merges, for every channel it writes, the maximum over the pixels it writes of
+ * (float bits & 0x7fffffff) of the value as stored into cmax[channel], uint32, indexed by the channel position in y as given -- the producers of one
+ * concat buffer pass cmax + their channel offset and fill one vector.  cmax is NOT zeroed here: the caller zeroes it once before the first producer.
+ * Unsigned maxima are order-free, so the vector equals pf_wino_absmax over the finished channels bit for bit; y is bit-identical with and without
+ * cmax.  cmax == NULL: exactly the plain call. */
+/* n uint32 words at p = 0, one memset on `stream` (the maxima vector before its first producer) */
+int pf_zero_u32(void* p, long n, void* stream);
+int pf_resize_bilinear_ex(const void* x, int x_ld, int B, int H, int W, int C, void* y, int y_ld, int OH, int OW,
+                          const void* add, int add_ld, int in_f32, int out_f32, int dtype, void* cmax, void* stream);
+int pf_resize_concat_ex(const void* const* xs, const int* lds, const int* Hs, const int* Ws, const int* Cs, int nsrc, int B,
+                        void* y, int y_ld, int OH, int OW, int dtype, void* cmax, void* stream);
+int pf_roi_align_ex(const void* feat, int f_ld, int Bf, int H, int W, int C, const float* rois, int K, void* y,
+                    int y_ld, int oh, int ow, float spatial_scale, int in_f32, int out_f32, int dtype, void* cmax, void* stream);
+int pf_copy_channels_ex(const void* x, int x_ld, void* y, int y_ld, long npix, int C, int in_f32, int out_f32,
+                        int dtype, void* cmax, void* stream);
 /* fusion-net input cat[coarse_depth_roi, fine_depth, rgb crop] (patchfusion.py:269) -> [B,h,w,8] (3 zero pad) */
 int pf_pack_fusion_input(const float* cdepth, const float* fdepth, const float* crops, void* y, int B, int h, int w,
                          int dtype, void* stream);

@@ -53,6 +53,11 @@ SIGNATURES = {
     "pf_roi_align": [vp, ci, ci, ci, ci, ci, vp, ci, vp, ci, ci, ci, cf, ci, ci, ci, vp],
     "pf_maxpool2": [vp, ci, ci, ci, ci, ci, vp, ci, ci, vp],
     "pf_copy_channels": [vp, ci, vp, ci, cl, ci, ci, ci, ci, vp],
+    "pf_resize_bilinear_ex": [vp, ci, ci, ci, ci, ci, vp, ci, ci, ci, vp, ci, ci, ci, ci, vp, vp],
+    "pf_resize_concat_ex": [C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, ci, vp, ci, ci, ci, ci, vp, vp],
+    "pf_roi_align_ex": [vp, ci, ci, ci, ci, ci, vp, ci, vp, ci, ci, ci, cf, ci, ci, ci, vp, vp],
+    "pf_copy_channels_ex": [vp, ci, vp, ci, cl, ci, ci, ci, ci, vp, vp],
+    "pf_zero_u32": [vp, cl, vp],
     "pf_pack_fusion_input": [vp, vp, vp, vp, ci, ci, ci, ci, vp],
     "pf_nhwc_to_nchw_f32": [vp, ci, vp, ci, ci, ci, ci, ci, ci, vp],
     "pf_conv_winograd": [C.POINTER(ConvParams), ci, vp, ci, ci, vp, vp, vp],
@@ -104,7 +109,7 @@ SIGNATURES = {
     "pf_depth_metrics": [vp, ci, ci, vp, ci, ci, vp, vp, cf, cf, ci, ci, ci, ci, vp, vp],
 }
 NON_STATUS = ("pf_last_error", "pf_version", "pf_percentile_workspace_bytes", "pf_conv_winograd_fused_supported", "pf_gemm_split3_route",
-              "pf_gemm_f16x2_points_route",
+              "pf_gemm_f16x2_points_route", "pf_gemm_f16x2_points_route_ex", "pf_conv_winograd_f16x2_supported_ex",
               "pf_wino_f16x2_scratch_bytes", "pf_conv_winograd_f16x2_supported", "pf_vit_attention_rpb_bf16_lds_bytes")   # entry points that do not return a status
 
 _lib = None
@@ -136,6 +141,10 @@ def load():
     lib.pf_gemm_split3_route.argtypes = [C.POINTER(ConvParams), ci]
     lib.pf_gemm_f16x2_points_route.restype = ci                # PF_S3_ROUTE_PERSIST192 / PERSIST128 (or -1), not a status
     lib.pf_gemm_f16x2_points_route.argtypes = [C.POINTER(ConvParams), ci]
+    lib.pf_gemm_f16x2_points_route_ex.restype = ci             # the same, for a layer whose channel maxima are handed in
+    lib.pf_gemm_f16x2_points_route_ex.argtypes = [C.POINTER(ConvParams), ci, ci]
+    lib.pf_conv_winograd_f16x2_supported_ex.restype = ci              # 1 / 0, not a status
+    lib.pf_conv_winograd_f16x2_supported_ex.argtypes = [C.POINTER(ConvParams), ci, ci, C.c_long, ci]
     lib.pf_wino_f16x2_scratch_bytes.restype = C.c_long                 # bytes, not a status
     lib.pf_wino_f16x2_scratch_bytes.argtypes = [ci, ci]
     lib.pf_conv_winograd_f16x2_supported.restype = ci                 # 1 / 0, not a status

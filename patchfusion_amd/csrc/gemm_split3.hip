@@ -1309,9 +1309,18 @@ int split3_route(const pf_conv_params& p, int cus) {
 //               1.19-1.26x at K >= 512 but 1.02-1.07x at K = 256 (cause not measured: no counter run; nominal V + M bytes over the time give 3.2 TB/s); the fp16x2 layer also pays the per-call range pass and U' split (three more launches), which 2128 tiles do not earn back
 //               (512->256 @ 8x56x74: 0.85x).  The thresholds are fitted to the shapes of the pass: nothing was timed between 2128 and 8288
 //               tiles nor at a K between 256 and 512.  PF_WINO_F16X2_N256 (A/B, read per call): 0 keeps these layers on the bf16x3 planes,
-//               1 and 2 = this rule (2: hip_ops keeps the range pass instead of the producer's maxima), 3 = every PERSIST128 layer.
+//               1 and 2 = this rule (2: hip_ops keeps the range pass instead of the producers' maxima), 3 = every PERSIST128 layer.
 //   -1          TILE64 / TILE128: fewer than two rounds of tiles, where a persistent fp16x2 walk measured 0.36-0.93x (round 8)
-int f16x2_points_route(const pf_conv_params& p, int cus) {
+//   maxima_given: the layer's channel maxima are handed in by the kernels that wrote its input (cmax_in of pf_conv_winograd_f16x2_windowed_ex: no memset,
+//               no range pass).  The producers are the output transform of a three-step layer (wino_output_cmax_kernel) and, from round 12 on,
+//               resize_src_kernel, roi_align_kernel and copy_channels_kernel (csrc/imageops.hip, the _ex entry points); channels written by a fused,
+//               direct or 1x1 conv (u5[..., :32] of the fusion decoder) still take the range pass, on that channel slice alone.  In the image pass the
+//               hand-over is worth 3.5 ms of 150.5 with the rule unchanged (profiles/r12_cmax_image_ab.md, r12_cmax_kernel_trace.md).  The range
+//               pass was what made the K = 256 and the small layers lose in the layer sweep (r11_n256_sweep.md column "maxima given": 1.04x at
+//               512->256 @ 2128 tiles ... 1.10x at 256->256), but widening the rule to K >= 256 and 2128 tiles for layers with given maxima measured
+//               0.3-1.5 ms in the image pass, each time under three times the run-to-run spread: NOT adopted.  It stays behind PF_WINO_F16X2_N256=5 (nothing timed between 2128
+//               and 8288 tiles, nor at a K between 256 and 512); at every other value maxima_given does not change the route.
+int f16x2_points_route(const pf_conv_params& p, int cus, bool maxima_given = false) {
   const int r = split3_route(p, cus);
   if (r == PF_S3_ROUTE_PERSIST192) return r;
   if (r != PF_S3_ROUTE_PERSIST128) return -1;
@@ -1319,7 +1328,9 @@ int f16x2_points_route(const pf_conv_params& p, int cus) {
   const char mode = s ? s[0] : '1';
   if (mode == '0') return -1;
   if (mode == '3') return r;
-  return p.Cin >= 512 && (long)p.B * p.OH * p.OW >= 4096 ? r : -1;
+  const long tiles = (long)p.B * p.OH * p.OW;
+  if (maxima_given && mode == '5') return p.Cin >= 256 && tiles >= 2128 ? r : -1;
+  return p.Cin >= 512 && tiles >= 4096 ? r : -1;
 }
 
 }  // namespace
@@ -1332,6 +1343,11 @@ extern "C" int pf_gemm_split3_route(const pf_conv_params* p, int cus) {
 extern "C" int pf_gemm_f16x2_points_route(const pf_conv_params* p, int cus) {
   if (!p || cus <= 0) return -1;
   return f16x2_points_route(*p, cus);
+}
+
+extern "C" int pf_gemm_f16x2_points_route_ex(const pf_conv_params* p, int cus, int maxima_given) {
+  if (!p || cus <= 0) return -1;
+  return f16x2_points_route(*p, cus, maxima_given != 0);
 }
 
 namespace {

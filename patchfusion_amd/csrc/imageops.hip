@@ -6,6 +6,11 @@
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
 
+// the range pass of the fp16x2 Winograd layers (csrc/wino_f16x2.hip; not part of the C ABI)
+namespace pf_f16x2 {
+int launch_absmax(const float* x, int x_ld, long P, int C, int relu_in, unsigned* cmax, hipStream_t st);
+}
+
 namespace {
 
 inline int grid_for(long n, int block) {
@@ -153,19 +158,58 @@ __device__ __forceinline__ void stv(T* p, const float (&v)[16 / sizeof(T)]) {
   else store8(p, v);
 }
 
+// ---- channel maxima of the values a kernel stores (CMAX = true instantiations) ---------------------------------------------------------------
+// The range pass of an fp16x2 Winograd layer (csrc/wino_f16x2.hip wino_absmax_kernel: m_c = max over the pixels of float bits & 0x7fffffff) reads its
+// whole input a second time; the kernel that WRITES that input has every value in registers.  Same scheme as wino_absmax_kernel and
+// wino_output_cmax_kernel: a running maximum in registers (kept while the thread stays on one channel vector), one atomicMax per channel into the
+// block's LDS copy, one global atomicMax per channel per block.  A uint max of non-negative float bits is order-free, so the merged vector equals the
+// range pass over the finished tensor bit for bit.  cmax is indexed by the channel position in the destination the kernel was given.
+template <int N>
+struct CmaxRun {
+  unsigned m[N];
+  int v = -1;                                           // the channel vector the maxima belong to (-1: none yet)
+  __device__ __forceinline__ void flush(unsigned* sm) {
+    if (v < 0) return;
+#pragma unroll
+    for (int e = 0; e < N; ++e)
+      if (m[e]) atomicMax(&sm[v * N + e], m[e]);
+  }
+  __device__ __forceinline__ void take(int vec, const float (&o)[N], unsigned* sm) {
+    if (vec != v) {
+      flush(sm);
+      v = vec;
+#pragma unroll
+      for (int e = 0; e < N; ++e) m[e] = 0u;
+    }
+#pragma unroll
+    for (int e = 0; e < N; ++e) m[e] = max(m[e], __float_as_uint(o[e]) & 0x7fffffffu);
+  }
+};
+// the block's LDS maxima into the global vector (after a __syncthreads); cmax only grows, so a plain read that already shows the value saves the atomic
+__device__ __forceinline__ void cmax_merge_block(const unsigned* sm, int C, unsigned* cmax) {
+  for (int i = threadIdx.x; i < C; i += blockDim.x)
+    if (sm[i] > cmax[i]) atomicMax(&cmax[i], sm[i]);
+}
+
 // Block: RPB consecutive source rows (b, r .. r + RPB - 1) of every source.  Per source the block first tabulates, in LDS, the output-column
 // range of every source column interval and the horizontal weights of every output column (they depend on neither b, r nor the channel).
 // A thread then owns a (column interval, channel vector) and walks DOWN its rows: the bottom taps of one row are the top taps of the next, so
 // a row costs two 16-byte loads (2.25 per row with the first), and per output pixel one LDS read, the blend and one 16-byte store.
 constexpr int RESIZE_RPB = 8;
-template <typename T>
+// CMAX: also merge the channel maxima of the stored values into cmax (uint32, indexed like the channels of y; the LDS copy [sum of s.C] follows wx)
+template <typename T, bool CMAX = false>
 __global__ void resize_src_kernel(ResizeSrc s0, ResizeSrc s1, ResizeSrc s2, int nsrc, int B, int Hmax, void* __restrict__ yv, int y_ld, int OH,
-                                  int OW, const void* __restrict__ addv, int add_ld, int Wmax, int rpb) {
+                                  int OW, const void* __restrict__ addv, int add_ld, int Wmax, int rpb, unsigned* __restrict__ cmax) {
   constexpr int N = 16 / sizeof(T);
   extern __shared__ __attribute__((aligned(16))) char resize_lds[];
   int2* rowrange = reinterpret_cast<int2*>(resize_lds);                                  // [RESIZE_RPB] output rows [x, y) of source row r
   int2* colrange = reinterpret_cast<int2*>(resize_lds + RESIZE_RPB * 8);                 // [Wmax]  output columns [x, y) of column interval c
   float2* wx = reinterpret_cast<float2*>(resize_lds + RESIZE_RPB * 8 + (size_t)Wmax * 8);  // [OW]    (l0, l1) of output column ox
+  unsigned* csm = reinterpret_cast<unsigned*>(resize_lds + RESIZE_RPB * 8 + (size_t)Wmax * 8 + (size_t)OW * 8);
+  const int ctot = s0.C + (nsrc > 1 ? s1.C : 0) + (nsrc > 2 ? s2.C : 0);
+  if constexpr (CMAX) {
+    for (int i = threadIdx.x; i < ctot; i += blockDim.x) csm[i] = 0u;      // (published by the barrier at the top of the source loop)
+  }
   T* __restrict__ y = reinterpret_cast<T*>(yv);
   const T* __restrict__ add = reinterpret_cast<const T*>(addv);
   const int tid = threadIdx.x, nthr = blockDim.x * gridDim.x, gtid = blockIdx.x * blockDim.x + tid;
@@ -182,6 +226,7 @@ __global__ void resize_src_kernel(ResizeSrc s0, ResizeSrc s1, ResizeSrc s2, int 
     const T* __restrict__ x = reinterpret_cast<const T*>(s.x);
     const int cv = s.C / N, n = s.W * cv;
     const float inv_cv = 1.0f / (float)cv;
+    CmaxRun<N> run;
     for (int g = blockIdx.y; g < B * gpi; g += gridDim.y) {              // block-uniform
       const int b = g / gpi, rbeg = (g - b * gpi) * rpb;
       const int rend = rbeg + rpb < s.H ? rbeg + rpb : s.H;
@@ -229,6 +274,7 @@ __global__ void resize_src_kernel(ResizeSrc s0, ResizeSrc s1, ResizeSrc s2, int 
                 for (int e = 0; e < N; ++e) o[e] = a[e] + o[e];
               }
               stv<T>(yp, o);
+              if constexpr (CMAX) run.take(v, o, csm + coff);
             }
           }
 #pragma unroll
@@ -236,7 +282,12 @@ __global__ void resize_src_kernel(ResizeSrc s0, ResizeSrc s1, ResizeSrc s2, int 
         }
       }
     }
+    if constexpr (CMAX) run.flush(csm + coff);
     coff += s.C;
+  }
+  if constexpr (CMAX) {
+    __syncthreads();
+    cmax_merge_block(csm, ctot, cmax);
   }
 }
 
@@ -264,10 +315,17 @@ __global__ void crop_resize_planar_kernel(const float* __restrict__ img, int C, 
 // Row-wise form (round 4): block (k, ph) = one output row of one ROI; the ROI geometry and the row's sample rows are computed once per block,
 // threads walk the row's (column, 8-channel vector) items with 32-bit arithmetic.  (The flat form spent its time in four 64-bit divisions per
 // 32-byte store: 2.9 TB/s = 36 % of HBM on a kernel that reads a 1/16 region and only has to stream its output.)
-template <typename T>
+// CMAX (float32 only): also merge the channel maxima of the stored values into cmax [C]; dynamic LDS = C words.
+template <typename T, bool CMAX = false>
 __global__ __launch_bounds__(256) void roi_align_kernel(const void* __restrict__ feat, int f_ld, int Bf, int H, int W, int C,
                                                         const float* __restrict__ rois, int K, void* __restrict__ y, int y_ld, int oh, int ow,
-                                                        float scale, int in_f32, int out_f32) {
+                                                        float scale, int in_f32, int out_f32, unsigned* __restrict__ cmax) {
+  extern __shared__ unsigned roi_csm[];
+  CmaxRun<8> run;
+  if constexpr (CMAX) {
+    for (int i = threadIdx.x; i < C; i += blockDim.x) roi_csm[i] = 0u;
+    __syncthreads();
+  }
   const int cv = (C + 7) >> 3;
   const int k = blockIdx.x / oh, ph = blockIdx.x - k * oh;
   const float* r = rois + k * 5;
@@ -328,7 +386,13 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const void* __restrict__
         for (int e = 0; e < 8; ++e) acc[e] /= count;
       }
       st8x<T>(y, (row_pix + pw) * y_ld + v * 8, out_f32, acc);
+      if constexpr (CMAX) run.take(v, acc, roi_csm);
     }
+  }
+  if constexpr (CMAX) {
+    run.flush(roi_csm);
+    __syncthreads();
+    cmax_merge_block(roi_csm, C, cmax);
   }
 }
 
@@ -395,9 +459,16 @@ __global__ void maxpool2_kernel(const T* __restrict__ x, int x_ld, int B, int H,
   }
 }
 
-template <typename T>
+// CMAX (float32 only): also merge the channel maxima of the copied values into cmax [C]; dynamic LDS = C words.
+template <typename T, bool CMAX = false>
 __global__ void copy_channels_kernel(const void* __restrict__ x, int x_ld, void* __restrict__ y, int y_ld, long npix, int C,
-                                     int in_f32, int out_f32) {
+                                     int in_f32, int out_f32, unsigned* __restrict__ cmax) {
+  extern __shared__ unsigned copy_csm[];
+  CmaxRun<8> run;
+  if constexpr (CMAX) {
+    for (int i = threadIdx.x; i < C; i += blockDim.x) copy_csm[i] = 0u;
+    __syncthreads();
+  }
   const int cv = C >> 3;
   const long total = npix * cv;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -406,6 +477,12 @@ __global__ void copy_channels_kernel(const void* __restrict__ x, int x_ld, void*
     float a[8];
     ld8x<T>(x, pix * x_ld + v * 8, in_f32, a);
     st8x<T>(y, pix * y_ld + v * 8, out_f32, a);
+    if constexpr (CMAX) run.take(v, a, copy_csm);
+  }
+  if constexpr (CMAX) {
+    run.flush(copy_csm);
+    __syncthreads();
+    cmax_merge_block(copy_csm, C, cmax);
   }
 }
 
@@ -797,6 +874,7 @@ __global__ __launch_bounds__(256, 2) void bins_tail_kernel(const float* __restri
 }  // namespace
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
+#define NOCMAX static_cast<unsigned*>(nullptr)
 #define LAUNCH_T(kern, total, ...)                                                                                      \
   do {                                                                                                                  \
     if (dtype == PF_DTYPE_BF16) hipLaunchKernelGGL(kern<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), __VA_ARGS__); \
@@ -821,17 +899,19 @@ static bool resize_v2() {
 // LDS = row ranges [8] + column ranges [Wmax] + weights [OW]
 constexpr int PF_RESIZE_V1 = -1;      // launch_resize_src: the source-aligned kernel's tables do not fit (W + OW above ~7.4k) -> use the v1 kernel
 template <typename T>
-static int launch_resize_src(const ResizeSrc* s, int nsrc, int B, void* y, int y_ld, int OH, int OW, const void* add, int add_ld, hipStream_t st) {
+static int launch_resize_src(const ResizeSrc* s, int nsrc, int B, void* y, int y_ld, int OH, int OW, const void* add, int add_ld, hipStream_t st,
+                             unsigned* cmax = nullptr) {
   constexpr int N = 16 / sizeof(T);
   int Hmax = 0, Wmax = 0;
-  long items = 0;
+  long items = 0, ctot = 0;
   for (int i = 0; i < nsrc; ++i) {
     Hmax = s[i].H > Hmax ? s[i].H : Hmax;
     Wmax = s[i].W > Wmax ? s[i].W : Wmax;
     const long it = (long)s[i].W * (s[i].C / N);
     items = it > items ? it : items;
+    ctot += s[i].C;
   }
-  const size_t lds = RESIZE_RPB * 8 + (size_t)Wmax * 8 + (size_t)OW * 8;
+  const size_t lds = RESIZE_RPB * 8 + (size_t)Wmax * 8 + (size_t)OW * 8 + (cmax ? (size_t)ctot * 4 : 0);      // (+ the block's channel maxima)
   if (items >= (1L << 22) || lds > 60000) return PF_RESIZE_V1;       // (very wide maps: the caller falls through to the output-walking kernels)
   // rows per block: 8 when that still leaves >= 4 blocks per CU, fewer for small maps
   const long gx = (items + 255) / 256 > 4 ? 4 : (items + 255) / 256;
@@ -840,29 +920,56 @@ static int launch_resize_src(const ResizeSrc* s, int nsrc, int B, void* y, int y
   long gy = (long)B * ((Hmax + rpb - 1) / rpb);
   gy = gy > 65535 ? 65535 : gy;
   const ResizeSrc none{};
+  if constexpr (sizeof(T) == 4) {
+    if (cmax) {
+      hipLaunchKernelGGL((resize_src_kernel<T, true>), dim3((unsigned)gx, (unsigned)gy), dim3(256), lds, st, s[0], nsrc > 1 ? s[1] : none,
+                         nsrc > 2 ? s[2] : none, nsrc, B, Hmax, y, y_ld, OH, OW, add, add_ld, Wmax, rpb, cmax);
+      return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
+    }
+  }
   hipLaunchKernelGGL(resize_src_kernel<T>, dim3((unsigned)gx, (unsigned)gy), dim3(256), lds, st, s[0], nsrc > 1 ? s[1] : none, nsrc > 2 ? s[2] : none,
-                     nsrc, B, Hmax, y, y_ld, OH, OW, add, add_ld, Wmax, rpb);
+                     nsrc, B, Hmax, y, y_ld, OH, OW, add, add_ld, Wmax, rpb, static_cast<unsigned*>(nullptr));
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
 }
 
-extern "C" int pf_resize_bilinear(const void* x, int x_ld, int B, int H, int W, int C, void* y, int y_ld, int OH, int OW,
-                                  const void* add, int add_ld, int in_f32, int out_f32, int dtype, void* stream) {
+// the output-walking resize kernels emit no maxima: when one of them ran for a call that asked for cmax, the range pass over the destination channels
+// it wrote gives the same vector (csrc/wino_f16x2.hip)
+static int cmax_by_range_pass(const void* y, int y_ld, long P, int C, unsigned* cmax, hipStream_t st) {
+  if (ok() != PF_OK) return PF_ERR_LAUNCH;
+  return pf_f16x2::launch_absmax(static_cast<const float*>(y), y_ld, P, C, 0, cmax, st);
+}
+
+// cmax != nullptr (float32 calls only): the channel maxima of the stored values are merged into cmax [C]
+static int resize_bilinear_impl(const void* x, int x_ld, int B, int H, int W, int C, void* y, int y_ld, int OH, int OW, const void* add, int add_ld,
+                                int in_f32, int out_f32, int dtype, unsigned* cmax, void* stream) {
   if (!x || !y || C % 8 || x_ld % 8 || y_ld % 8 || (add && add_ld % 8)) return PF_ERR_ARG;
+  if (cmax && dtype != PF_DTYPE_F32) return PF_ERR_ARG;
   const bool homogeneous = dtype == PF_DTYPE_BF16 ? (!in_f32 && !out_f32) : true;      // (dtype f32: everything is float32)
   if (homogeneous && resize_v2()) {
     const ResizeSrc s0{x, x_ld, H, W, C, ac_scale(H, OH), ac_scale(W, OW)};
     const int rc = dtype == PF_DTYPE_BF16 ? launch_resize_src<bf16_t>(&s0, 1, B, y, y_ld, OH, OW, add, add_ld, ST(stream))
-                                          : launch_resize_src<float>(&s0, 1, B, y, y_ld, OH, OW, add, add_ld, ST(stream));
+                                          : launch_resize_src<float>(&s0, 1, B, y, y_ld, OH, OW, add, add_ld, ST(stream), cmax);
     if (rc != PF_RESIZE_V1) return rc;
   }
   LAUNCH_ROWS(resize_bilinear_kernel, B * OH, OW * (C / 8), x, x_ld, B, H, W, C, y, y_ld, OH, OW, add, add_ld, in_f32, out_f32,
               ac_scale(H, OH), ac_scale(W, OW));
-  return ok();
+  return cmax ? cmax_by_range_pass(y, y_ld, (long)B * OH * OW, C, cmax, ST(stream)) : ok();
 }
 
-extern "C" int pf_resize_concat(const void* const* xs, const int* lds, const int* Hs, const int* Ws, const int* Cs, int nsrc, int B,
-                                void* y, int y_ld, int OH, int OW, int dtype, void* stream) {
+extern "C" int pf_resize_bilinear(const void* x, int x_ld, int B, int H, int W, int C, void* y, int y_ld, int OH, int OW,
+                                  const void* add, int add_ld, int in_f32, int out_f32, int dtype, void* stream) {
+  return resize_bilinear_impl(x, x_ld, B, H, W, C, y, y_ld, OH, OW, add, add_ld, in_f32, out_f32, dtype, nullptr, stream);
+}
+
+extern "C" int pf_resize_bilinear_ex(const void* x, int x_ld, int B, int H, int W, int C, void* y, int y_ld, int OH, int OW,
+                                     const void* add, int add_ld, int in_f32, int out_f32, int dtype, void* cmax, void* stream) {
+  return resize_bilinear_impl(x, x_ld, B, H, W, C, y, y_ld, OH, OW, add, add_ld, in_f32, out_f32, dtype, static_cast<unsigned*>(cmax), stream);
+}
+
+static int resize_concat_impl(const void* const* xs, const int* lds, const int* Hs, const int* Ws, const int* Cs, int nsrc, int B,
+                              void* y, int y_ld, int OH, int OW, int dtype, unsigned* cmax, void* stream) {
   if (!xs || !lds || !Hs || !Ws || !Cs || !y || nsrc < 2 || nsrc > 3 || y_ld % 8) return PF_ERR_ARG;
+  if (cmax && dtype != PF_DTYPE_F32) return PF_ERR_ARG;
   ResizeSrc s[3] = {};
   long cv = 0;
   for (int i = 0; i < nsrc; ++i) {
@@ -872,14 +979,23 @@ extern "C" int pf_resize_concat(const void* const* xs, const int* lds, const int
   }
   int cvmax = 0;
   for (int i = 0; i < nsrc; ++i) cvmax = Cs[i] / 8 > cvmax ? Cs[i] / 8 : cvmax;
-  (void)cv;
   if (resize_v2()) {
     const int rc = dtype == PF_DTYPE_BF16 ? launch_resize_src<bf16_t>(s, nsrc, B, y, y_ld, OH, OW, nullptr, 0, ST(stream))
-                                          : launch_resize_src<float>(s, nsrc, B, y, y_ld, OH, OW, nullptr, 0, ST(stream));
+                                          : launch_resize_src<float>(s, nsrc, B, y, y_ld, OH, OW, nullptr, 0, ST(stream), cmax);
     if (rc != PF_RESIZE_V1) return rc;
   }
   LAUNCH_ROWS(resize_concat_kernel, B * OH, OW * cvmax, s[0], s[1], s[2], nsrc, B, y, y_ld, OH, OW);
-  return ok();
+  return cmax ? cmax_by_range_pass(y, y_ld, (long)B * OH * OW, (int)(cv * 8), cmax, ST(stream)) : ok();
+}
+
+extern "C" int pf_resize_concat(const void* const* xs, const int* lds, const int* Hs, const int* Ws, const int* Cs, int nsrc, int B,
+                                void* y, int y_ld, int OH, int OW, int dtype, void* stream) {
+  return resize_concat_impl(xs, lds, Hs, Ws, Cs, nsrc, B, y, y_ld, OH, OW, dtype, nullptr, stream);
+}
+
+extern "C" int pf_resize_concat_ex(const void* const* xs, const int* lds, const int* Hs, const int* Ws, const int* Cs, int nsrc, int B,
+                                   void* y, int y_ld, int OH, int OW, int dtype, void* cmax, void* stream) {
+  return resize_concat_impl(xs, lds, Hs, Ws, Cs, nsrc, B, y, y_ld, OH, OW, dtype, static_cast<unsigned*>(cmax), stream);
 }
 
 extern "C" int pf_crop_resize_planar(const float* img, int C, int H, int W, const int* boxes, int P, float* out, int oh, int ow, void* stream) {
@@ -889,9 +1005,10 @@ extern "C" int pf_crop_resize_planar(const float* img, int C, int H, int W, cons
   return ok();
 }
 
-extern "C" int pf_roi_align(const void* feat, int f_ld, int Bf, int H, int W, int C, const float* rois, int K, void* y, int y_ld,
-                            int oh, int ow, float spatial_scale, int in_f32, int out_f32, int dtype, void* stream) {
+static int roi_align_impl(const void* feat, int f_ld, int Bf, int H, int W, int C, const float* rois, int K, void* y, int y_ld,
+                          int oh, int ow, float spatial_scale, int in_f32, int out_f32, int dtype, unsigned* cmax, void* stream) {
   if (!feat || !rois || !y) return PF_ERR_ARG;
+  if (cmax && (dtype != PF_DTYPE_F32 || C == 1 || C > 8192)) return PF_ERR_ARG;      // (maxima: float32 NHWC maps; one LDS word per channel)
   if (C == 1) {  // planar float depth map
     if (!in_f32 || !out_f32) return PF_ERR_ARG;
     hipLaunchKernelGGL(roi_align_scalar_kernel, dim3(grid_for((long)K * oh * ow, 256)), dim3(256), 0, ST(stream), (const float*)feat, Bf, H, W, rois, K, (float*)y, oh, ow, spatial_scale);
@@ -901,10 +1018,23 @@ extern "C" int pf_roi_align(const void* feat, int f_ld, int Bf, int H, int W, in
   if ((long)K * oh >= (1L << 31) || (long)(ow / 4 + 1) * (C / 8) >= (1L << 31)) return PF_ERR_ARG;
   const unsigned rows = (unsigned)((long)K * oh);
   if (dtype == PF_DTYPE_BF16)
-    hipLaunchKernelGGL(roi_align_kernel<bf16_t>, dim3(rows), dim3(256), 0, ST(stream), feat, f_ld, Bf, H, W, C, rois, K, y, y_ld, oh, ow, spatial_scale, in_f32, out_f32);
+    hipLaunchKernelGGL(roi_align_kernel<bf16_t>, dim3(rows), dim3(256), 0, ST(stream), feat, f_ld, Bf, H, W, C, rois, K, y, y_ld, oh, ow, spatial_scale, in_f32, out_f32, NOCMAX);
+  else if (cmax)
+    hipLaunchKernelGGL((roi_align_kernel<float, true>), dim3(rows), dim3(256), (size_t)C * 4, ST(stream), feat, f_ld, Bf, H, W, C, rois, K, y, y_ld, oh, ow,
+                       spatial_scale, in_f32, out_f32, cmax);
   else
-    hipLaunchKernelGGL(roi_align_kernel<float>, dim3(rows), dim3(256), 0, ST(stream), feat, f_ld, Bf, H, W, C, rois, K, y, y_ld, oh, ow, spatial_scale, in_f32, out_f32);
+    hipLaunchKernelGGL(roi_align_kernel<float>, dim3(rows), dim3(256), 0, ST(stream), feat, f_ld, Bf, H, W, C, rois, K, y, y_ld, oh, ow, spatial_scale, in_f32, out_f32, NOCMAX);
   return ok();
+}
+
+extern "C" int pf_roi_align(const void* feat, int f_ld, int Bf, int H, int W, int C, const float* rois, int K, void* y, int y_ld,
+                            int oh, int ow, float spatial_scale, int in_f32, int out_f32, int dtype, void* stream) {
+  return roi_align_impl(feat, f_ld, Bf, H, W, C, rois, K, y, y_ld, oh, ow, spatial_scale, in_f32, out_f32, dtype, nullptr, stream);
+}
+
+extern "C" int pf_roi_align_ex(const void* feat, int f_ld, int Bf, int H, int W, int C, const float* rois, int K, void* y, int y_ld,
+                               int oh, int ow, float spatial_scale, int in_f32, int out_f32, int dtype, void* cmax, void* stream) {
+  return roi_align_impl(feat, f_ld, Bf, H, W, C, rois, K, y, y_ld, oh, ow, spatial_scale, in_f32, out_f32, dtype, static_cast<unsigned*>(cmax), stream);
 }
 
 extern "C" int pf_maxpool2(const void* x, int x_ld, int B, int H, int W, int C, void* y, int y_ld, int dtype, void* stream) {
@@ -918,7 +1048,22 @@ extern "C" int pf_maxpool2(const void* x, int x_ld, int B, int H, int W, int C, 
 extern "C" int pf_copy_channels(const void* x, int x_ld, void* y, int y_ld, long npix, int C, int in_f32, int out_f32, int dtype, void* stream) {
   if (!x || !y || C % 8 || x_ld % 8 || y_ld % 8) return PF_ERR_ARG;
   const long total = npix * (C / 8);
-  LAUNCH_T(copy_channels_kernel, total, x, x_ld, y, y_ld, npix, C, in_f32, out_f32);
+  LAUNCH_T(copy_channels_kernel, total, x, x_ld, y, y_ld, npix, C, in_f32, out_f32, NOCMAX);
+  return ok();
+}
+
+extern "C" int pf_zero_u32(void* p, long n, void* stream) {
+  if (!p || n <= 0) return PF_ERR_ARG;
+  return hipMemsetAsync(p, 0, (size_t)n * 4, ST(stream)) == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
+}
+
+extern "C" int pf_copy_channels_ex(const void* x, int x_ld, void* y, int y_ld, long npix, int C, int in_f32, int out_f32, int dtype, void* cmax,
+                                   void* stream) {
+  if (!cmax) return pf_copy_channels(x, x_ld, y, y_ld, npix, C, in_f32, out_f32, dtype, stream);
+  if (!x || !y || C % 8 || x_ld % 8 || y_ld % 8 || dtype != PF_DTYPE_F32 || C > 8192) return PF_ERR_ARG;
+  const long total = npix * (C / 8);
+  hipLaunchKernelGGL((copy_channels_kernel<float, true>), dim3(grid_for(total, 256)), dim3(256), (size_t)C * 4, ST(stream), x, x_ld, y, y_ld, npix, C, in_f32,
+                     out_f32, static_cast<unsigned*>(cmax));
   return ok();
 }
 

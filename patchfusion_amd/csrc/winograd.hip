@@ -380,13 +380,13 @@ pf_conv_params f16x2_points_params(const pf_conv_params* p, const void* U2, int 
 }
 
 // The GEMM's tile is fixed by the product of the WHOLE layer (one window of all tiles), so every window size of a layer runs the same kernel.
-int f16x2_layer_route(const pf_conv_params* p, int u_rows) {
+int f16x2_layer_route(const pf_conv_params* p, int u_rows, bool maxima_given = false) {
   const long T = (long)p->B * ((p->H + 3) / 4) * ((p->W + 3) / 4);
   if (T > 0x7fffffffL) return -1;
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
   pf_conv_params q = f16x2_points_params(p, p->x, u_rows, const_cast<void*>(p->x), static_cast<float*>(p->y), T);
-  return pf_gemm_f16x2_points_route(&q, cus);
+  return pf_gemm_f16x2_points_route_ex(&q, cus, maxima_given ? 1 : 0);
 }
 
 // cmax_in != nullptr: the channel maxima of x (uint32 [Cin], of relu(x) when relu_in) are already known -- handed over by the producer's output
@@ -396,7 +396,7 @@ int f16x2_layer_route(const pf_conv_params* p, int u_rows) {
 int run_f16x2(const pf_conv_params* p, const float* U, int u_rows, void* V2, float* M, void* scratch, long window, hipStream_t st,
               const unsigned* cmax_in = nullptr, unsigned* cmax_out = nullptr, int cmax_relu = 0) {
   constexpr int MT = 4;
-  const bool t128 = f16x2_layer_route(p, u_rows) == PF_S3_ROUTE_PERSIST128;
+  const bool t128 = f16x2_layer_route(p, u_rows, cmax_in != nullptr) == PF_S3_ROUTE_PERSIST128;
   const int TH = (p->H + MT - 1) / MT, TW = (p->W + MT - 1) / MT;
   const long Tall = (long)p->B * TH * TW;
   if (Tall > 0x7fffffffL) return PF_ERR_ARG;
@@ -458,6 +458,12 @@ extern "C" long pf_wino_f16x2_scratch_bytes(int cin, int u_rows) {
 extern "C" int pf_conv_winograd_f16x2_supported(const pf_conv_params* p, int u_rows, int u_kpad, long window) {
   if (!f16x2_args_ok(p, u_rows, u_kpad, window)) return 0;
   return f16x2_layer_route(p, u_rows) >= 0 ? 1 : 0;
+}
+
+// the same for a call that will hand in the channel maxima (cmax_in): the rule of pf_gemm_f16x2_points_route_ex
+extern "C" int pf_conv_winograd_f16x2_supported_ex(const pf_conv_params* p, int u_rows, int u_kpad, long window, int maxima_given) {
+  if (!f16x2_args_ok(p, u_rows, u_kpad, window)) return 0;
+  return f16x2_layer_route(p, u_rows, maxima_given != 0) >= 0 ? 1 : 0;
 }
 
 extern "C" int pf_conv_winograd_f16x2_windowed(const pf_conv_params* p, const void* U, int u_rows, int u_kpad, void* V2, void* M, void* scratch,

@@ -597,14 +597,33 @@ class FusionNet:
         # --- coarse ROIs + fusion convs (patchfusion.py:240-267) ---
         cd_roi = ops.empty((B, 1, H, W), F32, dev)
         ops.roi_align_depth(coarse_depth, rois, cd_roi, 1.0)
+        # Channel maxima for the fp16x2 Winograd layers (hip_ops.cmax_begin): where the conv that reads a concat buffer would run that form, the
+        # kernels that WRITE the buffer merge the per-channel max |value| into one vector, slice by slice, and the conv skips its range pass (a second
+        # read of the whole buffer).  The vector is None for every other layer and for an ops backend without cmax_begin: then nothing changes.
+        begin = getattr(ops, "cmax_begin", None)
+        chain = getattr(ops, "conv_chain", None)
+
+        def cm_kw(cm, c0=None, c1=None):
+            return {} if cm is None else {"cmax": cm[c0:c1]}
+
+        def conv_pair(x, c0, t, c1, y, cm, cm_y=None):
+            """y = relu(conv(relu(conv(x)))) of a DoubleConv; t is read by the second conv alone, so the first hands over its maxima (conv_chain)"""
+            if chain is not None:
+                kw = {} if cm is None and cm_y is None else dict(cmax_in=cm, cmax_out=cm_y)
+                return chain(x, c0, t, c1, y, dict(pad=1, act="relu"), dict(pad=1, act="relu"), **kw)
+            ops.conv(x, c0, t, pad=1, act="relu")
+            ops.conv(t, c1, y, pad=1, act="relu")
+            return y
+
         guide = []
         for i in range(6):
             h, w = sizes[i]
             cat = ops.empty((B, h, w, 2 * ch[i]), dt, dev)
-            ops.roi_align(coarse_feats[i], rois, cat[..., :ch[i]], h / H)
-            ops.copy_channels(fine_feats[i], cat[..., ch[i]:])
             gc = ops.empty((B, h, w, ch[i]), dt, dev)
-            ops.conv(cat, self.fconv[i], gc, pad=1)
+            cm = begin(cat, self.fconv[i], gc, "cat", pad=1) if begin is not None else None
+            ops.roi_align(coarse_feats[i], rois, cat[..., :ch[i]], h / H, **cm_kw(cm, 0, ch[i]))
+            ops.copy_channels(fine_feats[i], cat[..., ch[i]:], **cm_kw(cm, ch[i], 2 * ch[i]))
+            ops.conv(cat, self.fconv[i], gc, pad=1, **({} if cm is None else {"cmax_in": cm}))
             guide.append(gc)
         # --- encoder (guided_fusion_model.py:178-184) ---
         inp = ops.empty((B, H, W, 8), dt, dev)
@@ -633,27 +652,33 @@ class FusionNet:
             h, w = sizes[i]
             c = ch[i]
             v = ops.empty((B, h, w, 2 * c), dt, dev)                 # cat[feat_enc, roi_align(g2l)]
+            tv_shape = (B, h, w, self.convs[i][0].cout)
+            # v's maxima: [the up conv's output transform | roi_align]  (the plan needs an output of tv's layout, not tv itself: it is allocated where
+            # it always was, after the up convs, so the peak allocation stays what it was)
+            cmv = begin(v, self.convs[i][0], ops.empty(tv_shape, dt, dev), "v", pad=1, act="relu") if begin is not None else None
             if i == 0:
-                ops.resize(enc[0], v[..., :c])
+                ops.resize(enc[0], v[..., :c], **cm_kw(cmv, 0, c))
             else:
                 cp = ch[i - 1]
                 u = u5 if i == 5 else ops.empty((B, h, w, c + 2 * cp), dt, dev)
-                # Upv1 concat buffer [enc resized to the DPT grid | up(temp) | up(guide)] in ONE launch (whole rows of u);
-                # at the last level enc already sits in u5[..., :32] (the inc conv wrote it there)
-                if i < 5:
-                    ops.resize_concat([enc[i], temp, guide[i - 1]], u)
-                else:
-                    ops.resize_concat([temp, guide[i - 1]], u[..., c:])
                 c0, c1 = self.upc[i - 1]
                 t = ops.empty((B, h, w, c0.cout), dt, dev)
-                ops.conv(u, c0, t, pad=1, act="relu")
-                ops.conv(t, c1, v[..., :c], pad=1, act="relu")
-            ops.roi_align(g2l[i], rois, v[..., c:], h / H)
+                cmu = begin(u, c0, t, "u", pad=1, act="relu") if begin is not None else None
+                # Upv1 concat buffer [enc resized to the DPT grid | up(temp) | up(guide)] in ONE launch (whole rows of u);
+                # at the last level enc already sits in u5[..., :32] (the inc conv wrote it there: its maxima take the range pass, on that slice alone)
+                if i < 5:
+                    ops.resize_concat([enc[i], temp, guide[i - 1]], u, **cm_kw(cmu))
+                else:
+                    if cmu is not None:
+                        ops.absmax(u[..., :c], cmu[:c])
+                    ops.resize_concat([temp, guide[i - 1]], u[..., c:], **cm_kw(cmu, c))
+                conv_pair(u, c0, t, c1, v[..., :c], cmu, None if cmv is None else cmv[:c])
+                t = None                                             # (free the up convs' intermediate before the next allocations, as before)
+            ops.roi_align(g2l[i], rois, v[..., c:], h / H, **cm_kw(cmv, c, 2 * c))
             c0, c1 = self.convs[i]
-            t = ops.empty((B, h, w, c0.cout), dt, dev)
-            ops.conv(v, c0, t, pad=1, act="relu")
+            tv = ops.empty(tv_shape, dt, dev)
             temp = clb[..., :32] if i == 5 else ops.empty((B, h, w, c1.cout), dt, dev)
-            ops.conv(t, c1, temp, pad=1, act="relu")
+            conv_pair(v, c0, tv, c1, temp, cmv)
             fused.append(temp)
             if taps is not None:
                 taps[f"gf_out{i}"] = temp

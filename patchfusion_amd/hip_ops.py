@@ -201,9 +201,11 @@ def _f16x2_scratch(device, nbytes):
 _WSCMAX = {}
 
 
-def _cmax_buffer(device, n):
-    """per-(device, stream) uint32 buffer for the channel maxima a three-step layer hands to the fp16x2 layer that reads its output next (conv_chain)"""
-    key = (device.index, torch.cuda.current_stream().cuda_stream)
+def _cmax_buffer(device, n, slot="t"):
+    """per-(device, stream, slot) uint32 buffer for the channel maxima handed to an fp16x2 layer by the kernels that write its input: slot "t" = the
+    intermediate of a conv_chain (filled by conv 1's output transform); the other slots are named by the caller of cmax_begin, one per input tensor
+    that is alive at the same time (launches of one stream are ordered, so a slot is free again once its consumer has been launched)"""
+    key = (device.index, torch.cuda.current_stream().cuda_stream, slot)
     t = _WSCMAX.get(key)
     if t is None or t.numel() < n:
         t = _WSCMAX[key] = torch.empty(max(n, 1024), dtype=torch.int32, device=device)
@@ -211,8 +213,17 @@ def _cmax_buffer(device, n):
 
 
 def _cmax_handover_enabled():
-    """PF_WINO_F16X2_N256=2 (and 0): every fp16x2 layer runs its own range pass (A/B of the hand-over alone)"""
+    """PF_WINO_F16X2_N256=2 (and 0): every fp16x2 layer runs its own range pass (A/B of the hand-over alone); 5: the hand-over, and the 128-tile
+    layers whose maxima are given take fp16x2 from K >= 256 and 2128 tiles on (measured, not adopted: csrc/gemm_split3.hip f16x2_points_route)"""
     return _env("PF_WINO_F16X2_N256", "1") not in ("0", "2")
+
+
+def _cmax_ptr(cmax, n):
+    """device pointer of a uint32 channel-maxima vector (int32 storage, unit stride, at least n entries), or None"""
+    if cmax is None:
+        return None
+    assert cmax.dtype == torch.int32 and cmax.dim() == 1 and cmax.stride(0) == 1 and cmax.numel() >= n, (cmax.dtype, cmax.shape, n)
+    return _p(cmax)
 
 
 def release_workspaces():
@@ -272,9 +283,11 @@ class HipOps:
 
     # ---------------- conv / linear ----------------
     @staticmethod
-    def _conv_plan(x, pw, y, stride, pad, act, relu_in, res, res2, direct):
+    def _conv_plan(x, pw, y, stride, pad, act, relu_in, res, res2, direct, given=False):
         """everything about a conv call that does not change while shapes / strides / the packed layer stay the same: the argument checks, the filled
-        pf_conv_params and the dispatch decision ('pp' | 's3_1x1' | 'fused' | 'wino3h' | 'wino3' | 'wino' | 'direct').  Cached by HipOps.conv per (layer, layout)."""
+        pf_conv_params and the dispatch decision ('pp' | 's3_1x1' | 'fused' | 'wino3h' | 'wino3' | 'wino' | 'direct').  Cached by HipOps.conv per (layer, layout).
+        given: the call will hand in the channel maxima of x (cmax_in) -- the route then follows pf_gemm_f16x2_points_route_ex (the same layers at
+        default switches; more 128-tile layers under PF_WINO_F16X2_N256=5)."""
         x4, y4 = _as4(x), _as4(y)
         B, H, W, _ = x4.shape
         OH = (H + 2 * pad - pw.KH) // stride + 1
@@ -325,7 +338,7 @@ class HipOps:
                 # (split: V holds three bf16 planes = 6 bytes per element instead of 4; whole tile octets, csrc/winograd.hip)
                 window, _, nV, nM = wino3_window(B, H, W, pw)
                 rows, kpad = pw.wino_u.shape[1], pw.wino_u.shape[2]
-                if _wino_f16x2_enabled() and _L.pf_conv_winograd_f16x2_supported(C.byref(p), rows, kpad, window):
+                if _wino_f16x2_enabled() and _L.pf_conv_winograd_f16x2_supported_ex(C.byref(p), rows, kpad, window, int(bool(given))):
                     # fp16x2 planes (the same windows; V: two fp16 planes = one float32 word per element)
                     return "wino3h", p, (_p(pw.wino_u), rows, kpad, 36 * window * pw.cin, nM, window, _L.pf_wino_f16x2_scratch_bytes(pw.cin, rows))
                 return "wino3", p, (_p(pw.wino_u3), pw.wino_u3.shape[3], pw.wino_u3.shape[2] * 32, nV, nM, window)
@@ -369,43 +382,83 @@ class HipOps:
             check(_L.pf_gemm_bf16_pp(C.byref(p), _stream()), "pf_gemm_bf16_pp")
 
     @staticmethod
-    def conv(x, pw: PackedConv, y, stride=1, pad=0, act=None, relu_in=False, res=None, res2=None, _timed=None, _direct=None):
+    def conv(x, pw: PackedConv, y, stride=1, pad=0, act=None, relu_in=False, res=None, res2=None, _timed=None, _direct=None, cmax_in=None):
         """y = epi(conv(x)) through the kernel the dispatch rules pick (pf_conv / fused or three-step Winograd / bf16 ping-pong GEMM).
         The plan of a call -- checks, filled pf_conv_params, route -- is cached per (packed layer, tensor layouts, epilogue); a repeat call only
         refreshes the four data pointers (round-3 review: 22 us of Python per library call, most of it here)."""
         if _timed is None and _direct is None:
-            ent = HipOps._conv_plan_cached(x, pw, y, stride, pad, act, relu_in, res, res2)
-            HipOps._conv_exec(ent[1], ent[2], ent[3], x.device)
+            ent = HipOps._conv_plan_cached(x, pw, y, stride, pad, act, relu_in, res, res2, cmax_in is not None)
+            if cmax_in is not None and ent[1] != "wino3h":
+                raise _lib.PfError("conv: cmax_in given to a layer that does not run the fp16x2 Winograd form (ask cmax_begin first)")
+            HipOps._conv_exec(ent[1], ent[2], ent[3], x.device, cmax_in=cmax_in)
             return y
+        assert cmax_in is None
         route, p, extra = HipOps._conv_plan(x, pw, y, stride, pad, act, relu_in, res, res2, _direct)
         return HipOps._conv_uncached(route, p, extra, x, y, _timed)
 
     @staticmethod
-    def conv_chain(x, pw1, t, pw2, y, kw1, kw2):
+    def cmax_begin(x, pw, y, slot, stride=1, pad=0, act=None, relu_in=False, res=None, res2=None):
+        """Will conv(x, pw, y, ...) run the fp16x2 Winograd form when the channel maxima of x are handed in?  Then: a zeroed uint32 vector [pw.cin]
+        (int32 storage; one memset on the current stream) that the kernels writing x fill slice by slice (resize / resize_concat / roi_align /
+        copy_channels with cmax=, absmax for channels another kernel wrote, conv_chain with cmax_out=) and that the conv takes as cmax_in= instead of
+        running its range pass.  Else None: write x and call conv as usual.  `slot` names the buffer: vectors alive at the same time need different
+        slots.  The maxima are those of the raw stored values, so a consumer with relu_in is refused."""
+        if relu_in or not _cmax_handover_enabled() or x.dtype != torch.float32 or x.shape[-1] != pw.cin:
+            return None
+        ent = HipOps._conv_plan_cached(x, pw, y, stride, pad, act, relu_in, res, res2, True)
+        if ent[1] != "wino3h":
+            return None
+        cm = _cmax_buffer(x.device, pw.cin, slot)[:pw.cin]
+        check(_L.pf_zero_u32(_p(cm), pw.cin, _stream()), "pf_zero_u32")
+        return cm
+
+    @staticmethod
+    def absmax(x, cmax):
+        """the range pass alone, on the channels of the NHWC float32 view x: merges max |x[..., c]| (float bits) into cmax[c] (not zeroed here)"""
+        x4 = _as4(x)
+        B, H, W, Cc = x4.shape
+        assert x4.dtype == torch.float32
+        check(_L.pf_wino_absmax(_p(x4), _ld(x4), B * H * W, Cc, 0, _cmax_ptr(cmax, Cc), _stream()), "pf_wino_absmax")
+
+    @staticmethod
+    def conv_chain(x, pw1, t, pw2, y, kw1, kw2, cmax_in=None, cmax_out=None):
         """t = conv(x, pw1, **kw1); y = conv(t, pw2, **kw2) for a t that conv 2 reads whole and unmodified and nothing else writes (RCU conv1 -> conv2).
-        When conv 1 is a three-step Winograd layer and conv 2 an fp16x2 one, conv 1's output transform hands over the channel maxima of t and conv 2
-        skips its range pass (csrc/wino_f16x2_n256.hip wino_output_cmax_kernel; same bits either way); otherwise exactly two conv calls."""
-        e1 = HipOps._conv_plan_cached(x, pw1, t, kw1.get("stride", 1), kw1.get("pad", 0), kw1.get("act"), kw1.get("relu_in", False), kw1.get("res"), kw1.get("res2"))
-        e2 = HipOps._conv_plan_cached(t, pw2, y, kw2.get("stride", 1), kw2.get("pad", 0), kw2.get("act"), kw2.get("relu_in", False), kw2.get("res"), kw2.get("res2"))
-        if e1[1] in ("wino3", "wino3h") and e2[1] == "wino3h" and t.shape[-1] == pw1.cout == pw2.cin and _cmax_handover_enabled():
+        When conv 1 is a three-step Winograd layer and conv 2 an fp16x2 one (by the rule for given maxima), conv 1's output transform hands over the channel
+        maxima of t and conv 2 skips its range pass (csrc/wino_f16x2_n256.hip wino_output_cmax_kernel; same bits either way); otherwise exactly two
+        conv calls.  cmax_in: the maxima of x from cmax_begin(x, pw1, t, ...).  cmax_out: a uint32 vector [pw2.cout] that receives the maxima of y
+        (a slice of the next consumer's vector): from conv 2's output transform when it is a three-step layer, else from the range pass over y."""
+        def plan(a, pw, b, kw, given):
+            return HipOps._conv_plan_cached(a, pw, b, kw.get("stride", 1), kw.get("pad", 0), kw.get("act"), kw.get("relu_in", False), kw.get("res"),
+                                            kw.get("res2"), given)
+        e1 = plan(x, pw1, t, kw1, cmax_in is not None)
+        if cmax_in is not None and e1[1] != "wino3h":
+            raise _lib.PfError("conv_chain: cmax_in given to a layer that does not run the fp16x2 Winograd form (ask cmax_begin first)")
+        e2 = None
+        if e1[1] in ("wino3", "wino3h") and t.shape[-1] == pw1.cout == pw2.cin and _cmax_handover_enabled():
+            e2 = plan(t, pw2, y, kw2, True)
+        three = ("wino3", "wino3h")
+        if e2 is not None and e2[1] == "wino3h":
             cm = _cmax_buffer(x.device, pw1.cout)
-            HipOps._conv_exec(e1[1], e1[2], e1[3], x.device, cmax_out=cm, cmax_out_relu=bool(kw2.get("relu_in", False)))
-            HipOps._conv_exec(e2[1], e2[2], e2[3], x.device, cmax_in=cm)
+            HipOps._conv_exec(e1[1], e1[2], e1[3], x.device, cmax_in=cmax_in, cmax_out=cm, cmax_out_relu=bool(kw2.get("relu_in", False)))
+            HipOps._conv_exec(e2[1], e2[2], e2[3], x.device, cmax_in=cm, cmax_out=cmax_out)
         else:
-            HipOps._conv_exec(e1[1], e1[2], e1[3], x.device)
-            HipOps._conv_exec(e2[1], e2[2], e2[3], x.device)
+            e2 = plan(t, pw2, y, kw2, False)
+            HipOps._conv_exec(e1[1], e1[2], e1[3], x.device, cmax_in=cmax_in)
+            HipOps._conv_exec(e2[1], e2[2], e2[3], x.device, cmax_out=cmax_out if e2[1] in three else None)
+            if cmax_out is not None and e2[1] not in three:
+                HipOps.absmax(y[..., :pw2.cout], cmax_out)
         return y
 
     @staticmethod
-    def _conv_plan_cached(x, pw, y, stride, pad, act, relu_in, res, res2):
+    def _conv_plan_cached(x, pw, y, stride, pad, act, relu_in, res, res2, given=False):
         key = (id(pw), x.shape, x.stride(), y.shape, y.stride(), stride, pad, act, relu_in, x.dtype, y.dtype, x.device,
                None if res is None else (res.shape, res.stride(), res.dtype), None if res2 is None else (res2.shape, res2.stride(), res2.dtype),
-               _align16(x, y, res, res2))
+               _align16(x, y, res, res2), bool(given))
         ent = _CONV_CACHE.get(key)
         if ent is None or ent[0] is not pw:
             if len(_CONV_CACHE) > 4096:
                 _CONV_CACHE.clear()
-            ent = (pw,) + HipOps._conv_plan(x, pw, y, stride, pad, act, relu_in, res, res2, None)
+            ent = (pw,) + HipOps._conv_plan(x, pw, y, stride, pad, act, relu_in, res, res2, None, given)
             _CONV_CACHE[key] = ent
         else:
             p = ent[2]
@@ -855,7 +908,8 @@ class HipOps:
 
     # ---------------- image ops ----------------
     @staticmethod
-    def resize(x, y, add=None, dtype=None):
+    def resize(x, y, add=None, dtype=None, cmax=None):
+        """cmax (float32 calls): a uint32 vector [C] into which the kernel merges the channel maxima of what it stores (HipOps.cmax_begin)"""
         x4, y4 = _as4(x), _as4(y)
         B, H, W, Cc = x4.shape
         _, OH, OW, _ = y4.shape
@@ -865,12 +919,17 @@ class HipOps:
         out_f32 = int(y4.dtype == torch.float32)
         if add is not None:
             assert add.dtype == y4.dtype
+        if cmax is not None:
+            check(_L.pf_resize_bilinear_ex(_p(x4), _ld(x4), B, H, W, Cc, _p(y4), _ld(y4), OH, OW, _p(add), _ld(add) if add is not None else 0,
+                                           in_f32, out_f32, code, _cmax_ptr(cmax, Cc), _stream()), "pf_resize_bilinear_ex")
+            return
         check(_L.pf_resize_bilinear(_p(x4), _ld(x4), B, H, W, Cc, _p(y4), _ld(y4), OH, OW, _p(add), _ld(add) if add is not None else 0,
                                     in_f32, out_f32, code, _stream()), "pf_resize_bilinear")
 
     @staticmethod
-    def resize_concat(xs, y):
-        """y[..., c0:c0+C_i] = bilinear(xs[i]) for 2 or 3 NHWC sources of the compute dtype (one launch, whole rows of y)"""
+    def resize_concat(xs, y, cmax=None):
+        """y[..., c0:c0+C_i] = bilinear(xs[i]) for 2 or 3 NHWC sources of the compute dtype (one launch, whole rows of y); cmax: as HipOps.resize,
+        indexed like the channels of y"""
         n = len(xs)
         y4 = _as4(y)
         B, OH, OW, Ct = y4.shape
@@ -879,6 +938,11 @@ class HipOps:
         arr = lambda v: (C.c_int * n)(*v)
         for t in list(xs) + [y4]:
             _p(t)
+        if cmax is not None:
+            check(_L.pf_resize_concat_ex(ptrs, arr([_ld(x) for x in xs]), arr([x.shape[1] for x in xs]), arr([x.shape[2] for x in xs]),
+                                         arr([x.shape[3] for x in xs]), n, B, _p(y4), _ld(y4), OH, OW, _dt(y4),
+                                         _cmax_ptr(cmax, sum(x.shape[3] for x in xs)), _stream()), "pf_resize_concat_ex")
+            return
         check(_L.pf_resize_concat(ptrs, arr([_ld(x) for x in xs]), arr([x.shape[1] for x in xs]), arr([x.shape[2] for x in xs]),
                                   arr([x.shape[3] for x in xs]), n, B, _p(y4), _ld(y4), OH, OW, _dt(y4), _stream()), "pf_resize_concat")
 
@@ -900,11 +964,16 @@ class HipOps:
               "pf_roi_align")
 
     @staticmethod
-    def roi_align(feat, rois, y, spatial_scale, dtype=None):
-        """feat [Bf,H,W,C] NHWC; rois f32 [K,5]; y [K,oh,ow,C]"""
+    def roi_align(feat, rois, y, spatial_scale, dtype=None, cmax=None):
+        """feat [Bf,H,W,C] NHWC; rois f32 [K,5]; y [K,oh,ow,C]; cmax: as HipOps.resize"""
         Bf, H, W, Cc = feat.shape
         K, oh, ow, _ = y.shape
         code = 1 if (dtype or feat.dtype) == torch.bfloat16 else 0
+        if cmax is not None:
+            check(_L.pf_roi_align_ex(_p(feat), _ld(feat), Bf, H, W, Cc, _p(rois), K, _p(y), _ld(y), oh, ow, float(spatial_scale),
+                                     int(feat.dtype == torch.float32), int(y.dtype == torch.float32), code, _cmax_ptr(cmax, Cc), _stream()),
+                  "pf_roi_align_ex")
+            return
         check(_L.pf_roi_align(_p(feat), _ld(feat), Bf, H, W, Cc, _p(rois), K, _p(y), _ld(y), oh, ow, float(spatial_scale),
                               int(feat.dtype == torch.float32), int(y.dtype == torch.float32), code, _stream()), "pf_roi_align")
 
@@ -914,10 +983,15 @@ class HipOps:
         check(_L.pf_maxpool2(_p(x), _ld(x), B, H, W, Cc, _p(y), _ld(y), _dt(x), _stream()), "pf_maxpool2")
 
     @staticmethod
-    def copy_channels(x, y):
+    def copy_channels(x, y, cmax=None):
+        """cmax: as HipOps.resize"""
         x4, y4 = _as4(x), _as4(y)
         B, H, W, Cc = x4.shape
         code = 1 if torch.bfloat16 in (x4.dtype, y4.dtype) else 0
+        if cmax is not None:
+            check(_L.pf_copy_channels_ex(_p(x4), _ld(x4), _p(y4), _ld(y4), B * H * W, Cc, int(x4.dtype == torch.float32),
+                                         int(y4.dtype == torch.float32), code, _cmax_ptr(cmax, Cc), _stream()), "pf_copy_channels_ex")
+            return
         check(_L.pf_copy_channels(_p(x4), _ld(x4), _p(y4), _ld(y4), B * H * W, Cc, int(x4.dtype == torch.float32),
                                   int(y4.dtype == torch.float32), code, _stream()), "pf_copy_channels")
 
