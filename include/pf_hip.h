@@ -420,6 +420,28 @@ int pf_depth_metrics(const float* gt, int H, int W, const float* pred, int ph, i
 int pf_silog_loss(const float* pred, const float* target, long n, float min_depth, float max_depth, float beta, double* ws3,
                   float* loss, void* stream);
 
+/* ---- evaluation side (csrc/evalops.hip): the tensors and images of the reference's evaluation loop that io.hip left on the host ---- */
+
+/* estimator/utils/image_ops.py:25-36 get_boundaries(disp, th, dilation) (duplicated at utils/metric.py:74-85; called by
+ * u4k_dataset.py:168 and general_dataset.py:75,84,94,121,133): disp is `planes` float32 planes [H][W], edges the same shape,
+ * 0.0f / 1.0f -- the `edges` argument of pf_depth_metrics.  A pixel is 1 when |v - neighbour| > th (float32 difference, strictly
+ * greater) for any of its up / down / left / right neighbours inside the image; comparisons with NaN are false.  dilation k > 0 then
+ * applies cv2.dilate(edges, ones((k, k)), iterations=1): anchor (k/2, k/2), out[y][x] = max over rows y-k/2 .. y-k/2+k-1 and columns
+ * x-k/2 .. x-k/2+k-1 (k = 10: -5 .. +4), pixels outside the image do not contribute.  One launch.  0 <= dilation <= 32 and
+ * H * W < 2^31, else PF_ERR_ARG.  disp and edges must not overlap. */
+int pf_depth_boundaries(const float* disp, int planes, int H, int W, float th, int dilation, float* edges, void* stream);
+
+/* pf_colorize_f32 with a choice of output layout.  PF_COLOR_RGBA: out is [n][4], the very bytes of pf_colorize_f32.  PF_COLOR_BGR: out is
+ * [n][3] = (B, G, R) of the same colours, the background colour included, alpha dropped; out must be 4-byte aligned.  BGR is both
+ * estimator/utils/color.py:22-23 (`colorize_infer_pfv1`: `value[:, :, :3][..., ::-1]`; pass use_invalid = 0 and no mask, it has no
+ * invalid handling) and estimator/tester/tester.py:69-71 (`colorize(...)[:, :, [2, 1, 0]]`, the array cv2.imwrite takes).
+ * The ranges of color.py:10-12 (min, 95th percentile) and :63-64 (min, max) come from pf_percentiles_f32 with use_invalid = 0 and
+ * q = 0 / 95 resp. 0 / 100: percentile 0 and 100 of the radix select are the extrema themselves.  Other layouts: PF_ERR_ARG. */
+#define PF_COLOR_RGBA 0
+#define PF_COLOR_BGR 1
+int pf_colorize_f32_ex(const float* depth, long n, const float* vmin_vmax, const uint8_t* lut_rgba, int N, float invalid_val,
+                       int use_invalid, const uint8_t* invalid_mask, uint32_t background_rgba, int layout, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,8 @@ SIGNATURES = {
     "pf_depth_to_u16": [vp, cl, cf, vp, vp],
     "pf_silog_loss": [vp, vp, cl, cf, cf, cf, vp, vp, vp],
     "pf_depth_metrics": [vp, ci, ci, vp, ci, ci, vp, vp, cf, cf, ci, ci, ci, ci, vp, vp],
+    "pf_depth_boundaries": [vp, ci, ci, ci, cf, ci, vp, vp],
+    "pf_colorize_f32_ex": [vp, cl, vp, vp, ci, cf, ci, vp, C.c_uint32, ci, vp, vp],
 }
 NON_STATUS = ("pf_last_error", "pf_version", "pf_percentile_workspace_bytes", "pf_conv_winograd_fused_supported", "pf_gemm_split3_route",
               "pf_gemm_f16x2_points_route", "pf_gemm_f16x2_points_route_ex", "pf_conv_winograd_f16x2_supported_ex",

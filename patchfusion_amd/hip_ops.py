@@ -1158,5 +1158,36 @@ class HipOps:
                                   float(min_depth), float(max_depth), y0, y1, x0, x1, _p(out13), _stream()), "pf_depth_metrics")
         return out13
 
+    # ---------------- evaluation side (evalops.hip) ----------------
+    MAX_DILATION = 32
+    COLOR_RGBA, COLOR_BGR = 0, 1
+
+    @staticmethod
+    def depth_boundaries(disp, th, dilation, out):
+        """get_boundaries (image_ops.py:25-36): disp [H,W] float32 -> out [H,W] float32 of 0 / 1 (the `edges` plane of depth_metrics);
+        dilation = side of the cv2.dilate box, 0 .. 32."""
+        assert disp.dtype == torch.float32 and disp.dim() == 2 and disp.is_contiguous()
+        assert out.dtype == torch.float32 and out.shape == disp.shape and out.is_contiguous() and out.data_ptr() != disp.data_ptr()
+        dilation = int(dilation)
+        if not 0 <= dilation <= HipOps.MAX_DILATION:
+            raise ValueError(f"dilation {dilation} outside 0 .. {HipOps.MAX_DILATION}")
+        check(_L.pf_depth_boundaries(_p(disp), 1, disp.shape[0], disp.shape[1], float(th), dilation, _p(out), _stream()), "pf_depth_boundaries")
+        return out
+
+    @staticmethod
+    def colorize_ex(depth, vmin_vmax, lut_rgba, N, invalid_val, background_rgba, out, invalid_mask=None, layout=0):
+        """colorize with an output layout: COLOR_RGBA -> out [n,4] (the bytes of colorize), COLOR_BGR -> out [n,3] = B, G, R"""
+        assert layout in (HipOps.COLOR_RGBA, HipOps.COLOR_BGR)
+        assert depth.dtype == torch.float32 and depth.is_contiguous() and vmin_vmax.dtype == torch.float32 and vmin_vmax.numel() == 2
+        assert lut_rgba.dtype == torch.uint8 and lut_rgba.shape == (N + 3, 4) and lut_rgba.is_contiguous()
+        assert out.dtype == torch.uint8 and out.numel() == depth.numel() * (4 if layout == HipOps.COLOR_RGBA else 3) and out.is_contiguous()
+        if invalid_mask is not None:
+            assert invalid_mask.dtype == torch.uint8 and invalid_mask.numel() == depth.numel() and invalid_mask.is_contiguous()
+        r, g, b, a = (int(v) & 255 for v in background_rgba)
+        check(_L.pf_colorize_f32_ex(_p(depth), depth.numel(), _p(vmin_vmax), _p(lut_rgba), int(N),
+                                    float(invalid_val if invalid_val is not None else 0.0), int(invalid_val is not None), _p(invalid_mask),
+                                    r | (g << 8) | (b << 16) | (a << 24), int(layout), _p(out), _stream()), "pf_colorize_f32_ex")
+        return out
+
 
 ops = HipOps()

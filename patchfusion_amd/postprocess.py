@@ -53,36 +53,40 @@ def gamma_table():
     return (np.power(np.arange(256) / 255, 2.2) * 255).astype(np.uint8)
 
 
-def colorize(value, vmin=None, vmax=None, cmap="turbo_r", invalid_val=-99, invalid_mask=None, background_color=(128, 128, 128, 255),
-             gamma_corrected=False, value_transform=None, vminp=2, vmaxp=95, ops=None):
-    """estimator/utils/color.py:95-150 on the device: -> uint8 tensor [H,W,4] (RGBA).  vmin / vmax default to the
-    exact 2nd / 95th percentile of the valid pixels (radix select, no sort, no host round trip).
+def _invalid_mask_u8(invalid_mask, d):
+    if invalid_mask is None:
+        return None
+    m = torch.as_tensor(np.asarray(invalid_mask.detach().cpu()) if isinstance(invalid_mask, torch.Tensor) else np.asarray(invalid_mask))
+    return (m.reshape(d.shape) != 0).to(torch.uint8).to(d.device).contiguous()
 
-    invalid_mask (bool, same grid; numpy or tensor) replaces the `value == invalid_val` test as in the reference (:121-122).
-    gamma_corrected is a per-byte function (:86-91), so it is applied to the 1 KiB colour table and the background colour, not to the
-    image.  value_transform is an arbitrary python callable on the normalised numpy array (:140-141): only in that case the
-    normalised plane makes one host round trip (the reference hands the callable a numpy array with NaN at the invalid pixels)."""
-    ops = ops or _ops()
-    d = _plane(value)
-    m = None
-    if invalid_mask is not None:
-        m = torch.as_tensor(np.asarray(invalid_mask.detach().cpu()) if isinstance(invalid_mask, torch.Tensor) else np.asarray(invalid_mask))
-        m = (m.reshape(d.shape) != 0).to(torch.uint8).to(d.device).contiguous()
+
+def _range(d, vmin, vmax, q0, q1, invalid_val, m, ops):
+    """device float32 [2] = (vmin, vmax); a None end is the q0 / q1 percentile of the pixels that invalid_val / m leave"""
     if vmin is None or vmax is None:
-        vmm = ops.percentiles(d, vminp, vmaxp, invalid_val=invalid_val, invalid_mask=m)
+        vmm = ops.percentiles(d, q0, q1, invalid_val=invalid_val, invalid_mask=m)
         if vmin is not None:
             vmm[0] = float(vmin)
         if vmax is not None:
             vmm[1] = float(vmax)
-    else:
-        vmm = torch.tensor([float(vmin), float(vmax)], dtype=torch.float32).to(d.device)
+        return vmm
+    return torch.tensor([float(vmin), float(vmax)], dtype=torch.float32).to(d.device)
+
+
+_LAYOUTS = {"rgba": (0, 4), "bgr": (1, 3)}
+
+
+def _render(d, m, vmm, cmap, invalid_val, background_color, gamma_corrected, value_transform, layout, ops):
+    """normalised colour lookup of plane d with range vmm -> uint8 [H,W,4] ('rgba') or [H,W,3] ('bgr')"""
+    if layout not in _LAYOUTS:
+        raise ValueError(f"layout {layout!r}: expected 'rgba' or 'bgr'")
     lut, N = colormap_lut(cmap, d.device)
     bg = tuple(int(v) & 255 for v in background_color)
     if gamma_corrected:
         g = gamma_table()
         lut = torch.from_numpy(g[lut.cpu().numpy()]).to(d.device).contiguous()
         bg = tuple(int(g[v]) for v in bg)
-    out = torch.empty(d.shape + (4,), dtype=torch.uint8, device=d.device)
+    code, ch = _LAYOUTS[layout]
+    out = torch.empty(d.shape + (ch,), dtype=torch.uint8, device=d.device)
     if value_transform is not None:
         if m is None:
             m = (d == invalid_val).to(torch.uint8) if invalid_val is not None else torch.zeros_like(d, dtype=torch.uint8)
@@ -93,7 +97,47 @@ def colorize(value, vmin=None, vmax=None, cmap="turbo_r", invalid_val=-99, inval
         x = np.ascontiguousarray(np.asarray(value_transform(x), dtype=np.float32))
         d = torch.from_numpy(x).to(d.device)
         vmm = torch.tensor([0.0, 1.0], dtype=torch.float32).to(d.device)        # (x - 0) / (1 - 0) == x exactly
-    return ops.colorize(d, vmm, lut, N, invalid_val, bg, out, invalid_mask=m)
+    if code == 0:
+        return ops.colorize(d, vmm, lut, N, invalid_val, bg, out, invalid_mask=m)
+    return ops.colorize_ex(d, vmm, lut, N, invalid_val, bg, out, invalid_mask=m, layout=code)
+
+
+def colorize(value, vmin=None, vmax=None, cmap="turbo_r", invalid_val=-99, invalid_mask=None, background_color=(128, 128, 128, 255),
+             gamma_corrected=False, value_transform=None, vminp=2, vmaxp=95, ops=None, layout="rgba"):
+    """estimator/utils/color.py:95-150 on the device: -> uint8 tensor [H,W,4] (RGBA).  vmin / vmax default to the
+    exact 2nd / 95th percentile of the valid pixels (radix select, no sort, no host round trip).
+
+    invalid_mask (bool, same grid; numpy or tensor) replaces the `value == invalid_val` test as in the reference (:121-122).
+    gamma_corrected is a per-byte function (:86-91), so it is applied to the 1 KiB colour table and the background colour, not to the
+    image.  value_transform is an arbitrary python callable on the normalised numpy array (:140-141): only in that case the
+    normalised plane makes one host round trip (the reference hands the callable a numpy array with NaN at the invalid pixels).
+    layout='bgr' writes uint8 [H,W,3] = `colorize(...)[:, :, [2, 1, 0]]` (tester.py:69-71, the array cv2.imwrite takes) directly."""
+    ops = ops or _ops()
+    d = _plane(value)
+    m = _invalid_mask_u8(invalid_mask, d)
+    vmm = _range(d, vmin, vmax, vminp, vmaxp, invalid_val, m, ops)
+    return _render(d, m, vmm, cmap, invalid_val, background_color, gamma_corrected, value_transform, layout, ops)
+
+
+def colorize_infer_pfv1(value, cmap="magma_r", vmin=None, vmax=None, ops=None):
+    """estimator/utils/color.py:8-25 on the device: -> uint8 tensor [H,W,3] in B, G, R order.  vmin defaults to the minimum and vmax to
+    the 95th percentile of ALL values (no invalid handling, :10-12); vmin == vmax maps every pixel to 0 (:16-17)."""
+    ops = ops or _ops()
+    d = _plane(value)
+    vmm = _range(d, vmin, vmax, 0, 95, None, None, ops)
+    return _render(d, None, vmm, cmap, None, (0, 0, 0, 0), False, None, "bgr", ops)
+
+
+def colorize_rescale(value, vmin=None, vmax=None, cmap="turbo_r", invalid_val=-99, invalid_mask=None, background_color=(128, 128, 128, 255),
+                     gamma_corrected=False, value_transform=None, vminp=2, vmaxp=95, ops=None):
+    """estimator/utils/color.py:28-93 on the device: -> uint8 tensor [H,W,4] (RGBA).  colorize with another range: vmin / vmax default
+    to the minimum / maximum over ALL values, invalid ones included (:63-64) -- what the reference computes, kept.  Invalid pixels
+    still go through the colormap's "bad" colour and end as background_color (:75,:84); vminp / vmaxp are accepted and unused as there."""
+    ops = ops or _ops()
+    d = _plane(value)
+    m = _invalid_mask_u8(invalid_mask, d)
+    vmm = _range(d, vmin, vmax, 0, 100, None, None, ops)
+    return _render(d, m, vmm, cmap, invalid_val, background_color, gamma_corrected, value_transform, "rgba", ops)
 
 
 def depth_to_uint16(depth, ops=None):
@@ -149,3 +193,89 @@ def compute_metrics(gt, pred, interpolate=True, garg_crop=False, eigen_crop=True
     if disp_gt_edges is not None:
         r["see"] = s[11] / s[12] if s[12] > 0 else 0.0
     return r
+
+
+def get_boundaries(disp, th=1., dilation=10, ops=None):
+    """estimator/utils/image_ops.py:25-36 (= utils/metric.py:74-85) on the device: -> float32 tensor [H,W] of 0 / 1, the `disp_gt_edges`
+    of compute_metrics.  1 where the disparity differs from an up / down / left / right neighbour by more than th; dilation k > 0
+    then dilates by a k x k box like cv2.dilate (anchor (k//2, k//2); 0 <= k <= 32, ValueError beyond)."""
+    ops = ops or _ops()
+    d = _plane(disp)
+    return ops.depth_boundaries(d, th, dilation, torch.empty_like(d))
+
+
+METRIC_KEYS = ("a1", "a2", "a3", "abs_rel", "rmse", "log_10", "rmse_log", "silog", "sq_rel", "see")
+
+
+class DepthEvaluator:
+    """The per-dataset evaluation loop (Tester.run -> dataset.get_metrics per image, dataset.evaluate -> pre_eval_to_metrics at the end,
+    u4k_dataset.py:185-213) without a host synchronisation per image: add() only queues kernels on the current stream, the 13 sums of
+    every image stay in one device buffer and results() / summary() fetch all of them with a single copy."""
+
+    def __init__(self, min_depth_eval, max_depth_eval, garg_crop=False, eigen_crop=False, dataset="", capacity=64, ops=None):
+        self.min_depth_eval, self.max_depth_eval = float(min_depth_eval), float(max_depth_eval)
+        self.garg_crop, self.eigen_crop, self.dataset = garg_crop, eigen_crop, dataset
+        self.capacity = max(1, int(capacity))
+        self._ops = ops
+        self._buf = None                       # [capacity, 13] float64 on the device of the first image
+        self._has_edges = []                   # per image, host side
+
+    def __len__(self):
+        return len(self._has_edges)
+
+    def add(self, depth_gt, pred, disp_gt=None, disp_gt_edges=None, additional_mask=None, th=1., dilation=0):
+        """Queue the metrics of one image (compute_metrics' arithmetic, pred resized to the ground-truth grid inside the kernel) into the
+        next row of the device buffer; with disp_gt instead of ready-made disp_gt_edges the boundary plane is made by get_boundaries
+        (th, dilation) first.  Performs NO host synchronisation and NO device-to-host copy as long as every tensor passed in already
+        lives on the device (a host tensor would have to be uploaded, which blocks); returns the index of the image."""
+        ops = self._ops or _ops()
+        g, p = _plane(depth_gt), _plane(pred)
+        e = None
+        if disp_gt_edges is not None:
+            e = _plane(disp_gt_edges.to(g.device))
+        elif disp_gt is not None:
+            e = get_boundaries(disp_gt.to(g.device), th, dilation, ops=ops)
+        if e is not None and e.shape != g.shape:
+            raise ValueError(f"edge plane {tuple(e.shape)} and ground truth {tuple(g.shape)} differ")
+        am = None
+        if additional_mask is not None:
+            am = (_plane_any(additional_mask.to(g.device)) != 0).to(torch.uint8).contiguous()
+        i = len(self._has_edges)
+        if self._buf is None:
+            self._buf = torch.zeros(self.capacity, 13, dtype=torch.float64, device=g.device)
+        elif i == self._buf.shape[0]:                                          # full: reallocate and copy on the device
+            self.capacity *= 2
+            buf = torch.zeros(self.capacity, 13, dtype=torch.float64, device=self._buf.device)
+            buf[:i].copy_(self._buf)
+            self._buf = buf
+        ops.depth_metrics(g, p, e, self.min_depth_eval, self.max_depth_eval,
+                          crop_rectangle(g.shape[0], g.shape[1], self.garg_crop, self.eigen_crop, self.dataset), self._buf[i], additional_mask=am)
+        self._has_edges.append(e is not None)
+        return i
+
+    def results(self):
+        """one device-to-host copy -> the list of dicts compute_metrics would have returned, image by image"""
+        n = len(self._has_edges)
+        if n == 0:
+            return []
+        out = []
+        for s, has_edges in zip(self._buf[:n].cpu().tolist(), self._has_edges):
+            r = metrics_from_sums(s)
+            if has_edges:
+                r["see"] = s[11] / s[12] if s[12] > 0 else 0.0
+            out.append(r)
+        return out
+
+    def summary(self):
+        """pre_eval_to_metrics (u4k_dataset.py:188-213): np.nanmean of every metric over the images, in the reference's key order.
+        `see` is averaged over the images that were given edges and left out when none was (the reference requires edges everywhere)."""
+        import warnings
+        res = self.results()
+        ret = {}
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)                    # "Mean of empty slice": nan, as in the reference
+            for k in METRIC_KEYS:
+                v = [r[k] for r in res if k in r]
+                if v or k != "see":
+                    ret[k] = float(np.nanmean(v)) if v else float("nan")
+        return ret
