@@ -311,7 +311,20 @@ __global__ void crop_resize_planar_kernel(const float* __restrict__ img, int C, 
 }
 
 // torchvision roi_align, aligned=True, sampling_ratio=-1 (adaptive).  Coordinates follow the
-// torchvision kernel's float32 operation order; __f*_rn intrinsics forbid FMA contraction.
+// torchvision kernel's float32 operation order, one rounding per operation.  (hipcc's __fmul_rn / __fadd_rn are a plain product and sum, which it
+// contracts into an fma: the coordinates then differ by an ulp from the float32 definition, 3e-5 of an output of a 28 x 37 map.  The pragma holds.)
+__device__ __forceinline__ float roi_edge(float r, float scale) {                  // r * scale - 0.5
+#pragma clang fp contract(off)
+  return r * scale - 0.5f;
+}
+__device__ __forceinline__ float roi_bin_start(float start, int p, float bin) {    // start + p * bin
+#pragma clang fp contract(off)
+  return start + (float)p * bin;
+}
+__device__ __forceinline__ float roi_sample(float bin_start, int i, float bin, int g) {   // bin_start + (i + .5) * bin / g
+#pragma clang fp contract(off)
+  return bin_start + ((float)i + 0.5f) * bin / (float)g;
+}
 // Row-wise form (round 4): block (k, ph) = one output row of one ROI; the ROI geometry and the row's sample rows are computed once per block,
 // threads walk the row's (column, 8-channel vector) items with 32-bit arithmetic.  (The flat form spent its time in four 64-bit divisions per
 // 32-byte store: 2.9 TB/s = 36 % of HBM on a kernel that reads a 1/16 region and only has to stream its output.)
@@ -330,15 +343,15 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const void* __restrict__
   const int k = blockIdx.x / oh, ph = blockIdx.x - k * oh;
   const float* r = rois + k * 5;
   const int b = (int)r[0];
-  const float start_w = __fsub_rn(__fmul_rn(r[1], scale), 0.5f), start_h = __fsub_rn(__fmul_rn(r[2], scale), 0.5f);
-  const float end_w = __fsub_rn(__fmul_rn(r[3], scale), 0.5f), end_h = __fsub_rn(__fmul_rn(r[4], scale), 0.5f);
+  const float start_w = roi_edge(r[1], scale), start_h = roi_edge(r[2], scale);
+  const float end_w = roi_edge(r[3], scale), end_h = roi_edge(r[4], scale);
   const float roi_w = __fsub_rn(end_w, start_w), roi_h = __fsub_rn(end_h, start_h);
   const float bin_h = __fdiv_rn(roi_h, (float)oh), bin_w = __fdiv_rn(roi_w, (float)ow);
   const int gh = (int)ceilf(__fdiv_rn(roi_h, (float)oh)), gw = (int)ceilf(__fdiv_rn(roi_w, (float)ow));
   const float count = (float)max(gh * gw, 1);
   const long base = (long)b * H * W;
   const long row_pix = ((long)k * oh + ph) * ow;
-  const float y_row = __fadd_rn(start_h, __fmul_rn((float)ph, bin_h));
+  const float y_row = roi_bin_start(start_h, ph, bin_h);
   // a thread owns RUN consecutive output columns of one 8-channel vector and keeps the four tap vectors of the last sample: with the up-sampling
   // ROIs of this path (a 1/16 region onto the full map: four output columns per source column, one sample per bin) three of four samples reuse
   // them -- the flat form re-fetched 4 KB of taps through the vector cache for every KB it stored, and THAT bounded it, not HBM
@@ -353,14 +366,14 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const void* __restrict__
     for (int q = 0; q < RUN; ++q) {
       const int pw = pg * RUN + q;
       if (pw >= ow) break;
-      const float x_col = __fadd_rn(start_w, __fmul_rn((float)pw, bin_w));
+      const float x_col = roi_bin_start(start_w, pw, bin_w);
       float acc[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) acc[e] = 0.f;
       for (int iy = 0; iy < gh; ++iy) {
-        const float yy = __fadd_rn(y_row, __fdiv_rn(__fmul_rn((float)iy + 0.5f, bin_h), (float)gh));
+        const float yy = roi_sample(y_row, iy, bin_h, gh);
         for (int ix = 0; ix < gw; ++ix) {
-          float xx = __fadd_rn(x_col, __fdiv_rn(__fmul_rn((float)ix + 0.5f, bin_w), (float)gw));
+          float xx = roi_sample(x_col, ix, bin_w, gw);
           float y2 = yy;
           if (y2 < -1.0f || y2 > (float)H || xx < -1.0f || xx > (float)W) continue;
           if (y2 <= 0.f) y2 = 0.f;
@@ -406,8 +419,8 @@ __global__ void roi_align_scalar_kernel(const float* __restrict__ feat, int Bf, 
     const int k = (int)(i / ((long)ow * oh));
     const float* r = rois + k * 5;
     const int b = (int)r[0];
-    const float start_w = __fsub_rn(__fmul_rn(r[1], scale), 0.5f), start_h = __fsub_rn(__fmul_rn(r[2], scale), 0.5f);
-    const float end_w = __fsub_rn(__fmul_rn(r[3], scale), 0.5f), end_h = __fsub_rn(__fmul_rn(r[4], scale), 0.5f);
+    const float start_w = roi_edge(r[1], scale), start_h = roi_edge(r[2], scale);
+    const float end_w = roi_edge(r[3], scale), end_h = roi_edge(r[4], scale);
     const float roi_w = __fsub_rn(end_w, start_w), roi_h = __fsub_rn(end_h, start_h);
     const float bin_h = __fdiv_rn(roi_h, (float)oh), bin_w = __fdiv_rn(roi_w, (float)ow);
     const int gh = (int)ceilf(__fdiv_rn(roi_h, (float)oh)), gw = (int)ceilf(__fdiv_rn(roi_w, (float)ow));
@@ -415,9 +428,9 @@ __global__ void roi_align_scalar_kernel(const float* __restrict__ feat, int Bf, 
     const float* src = feat + (long)b * H * W;
     float acc = 0.f;
     for (int iy = 0; iy < gh; ++iy) {
-      const float yy0 = __fadd_rn(__fadd_rn(start_h, __fmul_rn((float)ph, bin_h)), __fdiv_rn(__fmul_rn((float)iy + 0.5f, bin_h), (float)gh));
+      const float yy0 = roi_sample(roi_bin_start(start_h, ph, bin_h), iy, bin_h, gh);
       for (int ix = 0; ix < gw; ++ix) {
-        float xx = __fadd_rn(__fadd_rn(start_w, __fmul_rn((float)pw, bin_w)), __fdiv_rn(__fmul_rn((float)ix + 0.5f, bin_w), (float)gw));
+        float xx = roi_sample(roi_bin_start(start_w, pw, bin_w), ix, bin_w, gw);
         float y2 = yy0;
         if (y2 < -1.0f || y2 > (float)H || xx < -1.0f || xx > (float)W) continue;
         if (y2 <= 0.f) y2 = 0.f;
