@@ -442,6 +442,32 @@ int pf_depth_boundaries(const float* disp, int planes, int H, int W, float th, i
 int pf_colorize_f32_ex(const float* depth, long n, const float* vmin_vmax, const uint8_t* lut_rgba, int N, float invalid_val,
                        int use_invalid, const uint8_t* invalid_mask, uint32_t background_rgba, int layout, uint8_t* out, void* stream);
 
+/* ---- PNG encoding of the saved images (csrc/png.hip, csrc/png_huff.h): estimator/tester/tester.py:72,75-76 ---- */
+
+/* A device image [H][W][channels] of 8-bit samples (channels 1, 3 or 4: PNG colour types 0, 2, 6) or [H][W] of 16-bit samples
+ * (little-endian in memory, written big-endian) becomes the payload of one IDAT chunk minus its zlib wrapper: a sequence of deflate
+ * blocks, one dynamic-Huffman block of literals (no matches) + one empty stored block per band of PF_PNG_BAND_ROWS rows, all non-final.
+ * The caller adds the zlib header, a final empty stored block, the Adler-32 and the PNG chunks (postprocess.encode_png).  bgr != 0
+ * (channels 3 or 4) swaps channels 0 and 2 on read.  Other channels / bits combinations, bgr with one channel and rows of more than
+ * 2^28 - 1 bytes: PF_ERR_ARG.  Four steps:
+ *   1. pf_png_workspace_bytes: sizes of the device workspace and of the output buffer, and the number of bands.
+ *   2. pf_png_filter_histogram: picks each row's filter (None, Sub, Up or Paeth: smallest sum of |residual as int8|; kept in the
+ *      workspace) and fills hist257 (device, 257 counts: the bytes of the filtered stream, filter bytes included, [256] = number of bands).
+ *   3. pf_png_build_table: HOST ONLY, host pointers, no GPU call: hist257 -> table, PF_PNG_TABLE_WORDS words: [s] for s < 257 =
+ *      bit-reversed canonical Huffman code | length << 16 (1 .. 15, 0 = unused), [257] = bits of the block header, [260 ..] = the header
+ *      (BFINAL = 0, BTYPE = 2, HLIT = 0, HDIST = 0 with one distance code of length 0, HCLEN, code-length code, run symbols), at most 256 bytes.
+ *   4. pf_png_encode: table on the device (8-byte aligned), same image arguments and workspace as step 2.  out receives the bands back
+ *      to back; meta (device, 2 + 3 * nbands words) = total bytes (low, high), then per band {bytes, S1, S2} with S1 = sum of the band's
+ *      stream bytes and S2 = sum of (n - i) * byte i over its n bytes, both mod 65521 (the Adler-32 partial sums).
+ * workspace must be 16-byte aligned; its contents carry from step 2 to step 4. */
+#define PF_PNG_BAND_ROWS 8
+#define PF_PNG_TABLE_WORDS 324
+int pf_png_workspace_bytes(int H, int W, int channels, int bits, long* workspace_bytes, long* out_bytes, int* nbands);
+int pf_png_filter_histogram(const void* img, int H, int W, int channels, int bits, int bgr, void* workspace, uint32_t* hist257, void* stream);
+int pf_png_build_table(const uint32_t* hist257, uint32_t* table);
+int pf_png_encode(const void* img, int H, int W, int channels, int bits, int bgr, const uint32_t* table, void* workspace, uint8_t* out,
+                  uint32_t* meta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,11 @@ SIGNATURES = {
     "pf_depth_metrics": [vp, ci, ci, vp, ci, ci, vp, vp, cf, cf, ci, ci, ci, ci, vp, vp],
     "pf_depth_boundaries": [vp, ci, ci, ci, cf, ci, vp, vp],
     "pf_colorize_f32_ex": [vp, cl, vp, vp, ci, cf, ci, vp, C.c_uint32, ci, vp, vp],
+    # PNG encoding of the saved images (png.hip); pf_png_build_table is host-only: host pointers, no GPU call
+    "pf_png_workspace_bytes": [ci, ci, ci, ci, C.POINTER(cl), C.POINTER(cl), C.POINTER(ci)],
+    "pf_png_filter_histogram": [vp, ci, ci, ci, ci, ci, vp, vp, vp],
+    "pf_png_build_table": [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "pf_png_encode": [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp],
 }
 NON_STATUS = ("pf_last_error", "pf_version", "pf_percentile_workspace_bytes", "pf_conv_winograd_fused_supported", "pf_gemm_split3_route",
               "pf_gemm_f16x2_points_route", "pf_gemm_f16x2_points_route_ex", "pf_conv_winograd_f16x2_supported_ex",

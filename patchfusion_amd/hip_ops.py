@@ -1189,5 +1189,65 @@ class HipOps:
                                     r | (g << 8) | (b << 16) | (a << 24), int(layout), _p(out), _stream()), "pf_colorize_f32_ex")
         return out
 
+    # ---------------- PNG encoding of the saved images (png.hip) ----------------
+    PNG_BAND_ROWS, PNG_TABLE_WORDS = 8, 324
+
+    @staticmethod
+    def png_format(image, bgr=False):
+        """uint8 [H,W] / [H,W,3] / [H,W,4] or uint16 [H,W] -> (H, W, channels, bits, bgr)"""
+        if image.dtype == torch.uint8 and image.dim() in (2, 3):
+            ch, bits = (1 if image.dim() == 2 else int(image.shape[2])), 8
+        elif image.dtype == torch.uint16 and image.dim() == 2:
+            ch, bits = 1, 16
+        else:
+            raise ValueError(f"png: expected uint8 [H,W], [H,W,3], [H,W,4] or uint16 [H,W], got {image.dtype} {tuple(image.shape)}")
+        if ch not in (1, 3, 4) or image.shape[0] < 1 or image.shape[1] < 1:
+            raise ValueError(f"png: unsupported shape {tuple(image.shape)}")
+        if bgr and ch < 3:
+            raise ValueError("png: bgr needs three or four channels")
+        assert image.is_contiguous()
+        return int(image.shape[0]), int(image.shape[1]), ch, bits, int(bool(bgr))
+
+    @staticmethod
+    def png_workspace(image, bgr=False):
+        """-> (workspace bytes, output bytes, number of bands) of the PNG encoder for this image"""
+        H, W, ch, bits, _ = HipOps.png_format(image, bgr)
+        ws, ob, nb = C.c_long(), C.c_long(), C.c_int()
+        check(_L.pf_png_workspace_bytes(H, W, ch, bits, C.byref(ws), C.byref(ob), C.byref(nb)), "pf_png_workspace_bytes")
+        return ws.value, ob.value, nb.value
+
+    @staticmethod
+    def png_filter_histogram(image, workspace, hist, bgr=False):
+        """pass A: the row filters go into `workspace` (uint8, png_workspace bytes), the 257 counts into `hist` (int32 [257], device)"""
+        H, W, ch, bits, bgr = HipOps.png_format(image, bgr)
+        assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.numel() >= HipOps.png_workspace(image)[0]
+        assert hist.dtype == torch.int32 and hist.numel() == 257 and hist.is_contiguous()
+        check(_L.pf_png_filter_histogram(_p(image), H, W, ch, bits, bgr, _p(workspace), _p(hist), _stream()), "pf_png_filter_histogram")
+        return hist
+
+    @staticmethod
+    def png_build_table(hist):
+        """host step: 257 counts (sequence / numpy / host tensor) -> numpy uint32 [PNG_TABLE_WORDS] (codes, header bits, header)"""
+        import numpy as np
+        h = np.ascontiguousarray(np.asarray(hist, dtype=np.int64).reshape(-1).astype(np.uint32))
+        assert h.size == 257
+        table = np.zeros(HipOps.PNG_TABLE_WORDS, dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        check(_L.pf_png_build_table(h.ctypes.data_as(u32p), table.ctypes.data_as(u32p)), "pf_png_build_table")
+        return table
+
+    @staticmethod
+    def png_encode(image, table, workspace, out, meta, bgr=False):
+        """pass B + C: table int32 [PNG_TABLE_WORDS] on the device; out uint8 (png_workspace output bytes) receives the deflate blocks of
+        all bands back to back, meta int32 [2 + 3 * bands] the total size and each band's {bytes, Adler S1, S2}"""
+        H, W, ch, bits, bgr = HipOps.png_format(image, bgr)
+        assert table.dtype == torch.int32 and table.numel() == HipOps.PNG_TABLE_WORDS and table.is_contiguous()
+        ws_bytes, out_bytes, nbands = HipOps.png_workspace(image)
+        assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.numel() >= ws_bytes
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= out_bytes
+        assert meta.dtype == torch.int32 and meta.is_contiguous() and meta.numel() >= 2 + 3 * nbands
+        check(_L.pf_png_encode(_p(image), H, W, ch, bits, bgr, _p(table), _p(workspace), _p(out), _p(meta), _stream()), "pf_png_encode")
+        return out, meta
+
 
 ops = HipOps()

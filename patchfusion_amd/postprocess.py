@@ -4,6 +4,9 @@ depth tensor where it already lives.  Same names and arguments as the reference 
 small device tensors / python floats (one 104-byte D2H for the metrics).  There is no CPU path.
 """
 import math
+import os
+import struct
+import zlib
 
 import numpy as np
 import torch
@@ -145,6 +148,57 @@ def depth_to_uint16(depth, ops=None):
     ops = ops or _ops()
     d = _plane(depth)
     return ops.depth_to_u16(d, torch.empty(d.shape, dtype=torch.uint16, device=d.device))
+
+
+def _png_chunk(kind, data):
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(data, zlib.crc32(kind)))
+
+
+def encode_png(image, bgr=False, ops=None):
+    """A device image -> the bytes of a PNG file.  image: uint8 [H,W], [H,W,3], [H,W,4] (grey, RGB, RGBA) or torch.uint16 [H,W];
+    bgr=True reads channels 0 and 2 swapped, so `colorize(..., layout='bgr')` (the array cv2.imwrite takes, tester.py:69-72) gives the
+    file cv2 writes.  Row filters, histogram, Huffman coding and compaction run on the device (csrc/png.hip); the host builds the code
+    table from 257 counts (1 KB down, 1.3 KB up), reads the band sizes and Adler-32 partial sums (12 bytes per band of 8 rows) and the
+    compressed bytes, combines the Adler-32 and computes the chunk CRC-32s over the compressed bytes: container checksums, not compute."""
+    ops = ops or _ops()
+    img = image.detach().contiguous()
+    H, W, ch, bits, _ = ops.png_format(img, bgr)
+    ws_bytes, out_bytes, nbands = ops.png_workspace(img, bgr)
+    dev = img.device
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    hist = torch.empty(257, dtype=torch.int32, device=dev)
+    ops.png_filter_histogram(img, ws, hist, bgr)
+    table = ops.png_build_table(hist.cpu().numpy().view(np.uint32))
+    out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
+    meta = torch.empty(2 + 3 * nbands, dtype=torch.int32, device=dev)
+    ops.png_encode(img, torch.from_numpy(table.view(np.int32)).to(dev), ws, out, meta, bgr)
+    m = meta.cpu().numpy().view(np.uint32).tolist()
+    total = m[0] | (m[1] << 32)
+    assert total == sum(m[2::3]) and total <= out_bytes, (total, out_bytes)
+    body = out[:total].cpu().numpy().tobytes()
+    a, b, stride = 1, 0, W * ch * bits // 8 + 1
+    for k in range(nbands):                                                 # Adler-32 of the whole stream from the band partials
+        n = min(ops.PNG_BAND_ROWS, H - k * ops.PNG_BAND_ROWS) * stride
+        b += n * a + m[2 + 3 * k + 2]
+        a += m[2 + 3 * k + 1]
+    adler = ((b % 65521) << 16) | (a % 65521)
+    idat = b"\x78\x01" + body + b"\x01\x00\x00\xff\xff" + struct.pack(">I", adler)     # zlib header, bands, final empty stored block
+    ihdr = struct.pack(">IIBBBBB", W, H, bits, {1: 0, 3: 2, 4: 6}[ch], 0, 0, 0)
+    return b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", ihdr) + _png_chunk(b"IDAT", idat) + _png_chunk(b"IEND", b"")
+
+
+def save_prediction(result, work_dir, basename, gray_scale=False, ops=None):
+    """tester.py:66-76 with both encodes on the device: `{basename}.png` decodes to colorize(result, cmap='magma_r' | 'gray_r')[..., :3]
+    (what cv2.imwrite makes of the BGR array) and `{basename}_uint16.png` to (depth * 256).astype('uint16').  -> the two paths."""
+    ops = ops or _ops()
+    colour = colorize(result, cmap="gray_r" if gray_scale else "magma_r", ops=ops, layout="bgr")
+    colour_path = os.path.join(work_dir, f"{basename}.png")
+    uint16_path = os.path.join(work_dir, f"{basename}_uint16.png")
+    with open(colour_path, "wb") as f:
+        f.write(encode_png(colour, bgr=True, ops=ops))
+    with open(uint16_path, "wb") as f:
+        f.write(encode_png(depth_to_uint16(result, ops=ops), ops=ops))
+    return colour_path, uint16_path
 
 
 def crop_rectangle(gh, gw, garg_crop, eigen_crop, dataset):
