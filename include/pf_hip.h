@@ -468,6 +468,32 @@ int pf_png_build_table(const uint32_t* hist257, uint32_t* table);
 int pf_png_encode(const void* img, int H, int W, int channels, int bits, int bgr, const uint32_t* table, void* workspace, uint8_t* out,
                   uint32_t* meta, void* stream);
 
+/* ---- run matches for the same two files (csrc/png_rle.hip, csrc/png_huff.h): estimator/tester/tester.py:66-76 ---- */
+
+/* The same images, bands, meta and container as above, with every run of equal bytes inside a row of the filtered stream coded as
+ * deflate matches at distance 1 (zlib's Z_RLE): the first byte of a run is a literal, the rest is cut into chunks of 258, a chunk of
+ * 3 or more bytes is one match, a trailing chunk of 1 or 2 bytes is literals.  Pays on the colour image, loses on the 16-bit one, so
+ * step 2 counts for both codings at once and the caller chooses (postprocess.encode_png, strategy = 'huffman' | 'rle' | 'auto').
+ *   1. pf_png_rle_workspace_bytes: as pf_png_workspace_bytes, sized for the larger slot of the two codings: the workspace and the
+ *      output buffer serve pf_png_encode as well as pf_png_rle_encode.
+ *   2. pf_png_rle_filter_histogram: pf_png_filter_histogram's filter choice; hist (device, 8-byte aligned, PF_PNG_RLE_HIST_WORDS
+ *      words): [0 .. 256] the literal histogram pf_png_filter_histogram gives, [257 .. 542] the 286 token counts under the rule above
+ *      (literals, [257 + 256] = number of bands, then matches by length symbol 257 .. 285), [543] zero, [544 .. 545] the total of the
+ *      matches' extra bits (64 bits, low word first).
+ *   3. pf_png_rle_build_table: HOST ONLY: the 286 token counts -> table, PF_PNG_RLE_TABLE_WORDS words: [s] for s < 286 = bit-reversed
+ *      code | length << 16 (1 .. 14, 0 = unused), [286] = bits of the block header, [287] = the distance code (0 | 1 << 16),
+ *      [288 + k] = base length | extra bits << 16 of length symbol 257 + k, [320 ..] = the header (HLIT <= 29, HDIST = 0 with one
+ *      distance code of length 1), at most 272 bytes.
+ *   4. pf_png_rle_encode: as pf_png_encode, with the table of step 3. */
+#define PF_PNG_RLE_TABLE_WORDS 388
+#define PF_PNG_RLE_HIST_WORDS 546
+int pf_png_rle_workspace_bytes(int H, int W, int channels, int bits, long* workspace_bytes, long* out_bytes, int* nbands);
+int pf_png_rle_filter_histogram(const void* img, int H, int W, int channels, int bits, int bgr, void* workspace, uint32_t* hist,
+                                void* stream);
+int pf_png_rle_build_table(const uint32_t* hist286, uint32_t* table);
+int pf_png_rle_encode(const void* img, int H, int W, int channels, int bits, int bgr, const uint32_t* table, void* workspace,
+                      uint8_t* out, uint32_t* meta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,11 @@ SIGNATURES = {
     "pf_png_filter_histogram": [vp, ci, ci, ci, ci, ci, vp, vp, vp],
     "pf_png_build_table": [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
     "pf_png_encode": [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp],
+    # the same with run matches (png_rle.hip); pf_png_rle_build_table is host-only too
+    "pf_png_rle_workspace_bytes": [ci, ci, ci, ci, C.POINTER(cl), C.POINTER(cl), C.POINTER(ci)],
+    "pf_png_rle_filter_histogram": [vp, ci, ci, ci, ci, ci, vp, vp, vp],
+    "pf_png_rle_build_table": [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "pf_png_rle_encode": [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp],
 }
 NON_STATUS = ("pf_last_error", "pf_version", "pf_percentile_workspace_bytes", "pf_conv_winograd_fused_supported", "pf_gemm_split3_route",
               "pf_gemm_f16x2_points_route", "pf_gemm_f16x2_points_route_ex", "pf_conv_winograd_f16x2_supported_ex",

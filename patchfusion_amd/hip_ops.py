@@ -1249,5 +1249,49 @@ class HipOps:
         check(_L.pf_png_encode(_p(image), H, W, ch, bits, bgr, _p(table), _p(workspace), _p(out), _p(meta), _stream()), "pf_png_encode")
         return out, meta
 
+    # ---------------- the same with run matches at distance 1 (png_rle.hip) ----------------
+    PNG_RLE_TABLE_WORDS, PNG_RLE_HIST_WORDS = 388, 546
+
+    @staticmethod
+    def png_rle_workspace(image, bgr=False):
+        """png_workspace sized for the larger slot of the two codings: serves png_encode as well as png_rle_encode"""
+        H, W, ch, bits, _ = HipOps.png_format(image, bgr)
+        ws, ob, nb = C.c_long(), C.c_long(), C.c_int()
+        check(_L.pf_png_rle_workspace_bytes(H, W, ch, bits, C.byref(ws), C.byref(ob), C.byref(nb)), "pf_png_rle_workspace_bytes")
+        return ws.value, ob.value, nb.value
+
+    @staticmethod
+    def png_rle_filter_histogram(image, workspace, hist, bgr=False):
+        """pass A': png_filter_histogram's filters; hist (int32 [PNG_RLE_HIST_WORDS], device) = 257 literal counts, 286 token counts
+        from [257], the matches' extra bits as 64 bits from [544]"""
+        H, W, ch, bits, bgr = HipOps.png_format(image, bgr)
+        assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.numel() >= HipOps.png_rle_workspace(image)[0]
+        assert hist.dtype == torch.int32 and hist.numel() == HipOps.PNG_RLE_HIST_WORDS and hist.is_contiguous()
+        check(_L.pf_png_rle_filter_histogram(_p(image), H, W, ch, bits, bgr, _p(workspace), _p(hist), _stream()), "pf_png_rle_filter_histogram")
+        return hist
+
+    @staticmethod
+    def png_rle_build_table(hist):
+        """host step: 286 token counts -> numpy uint32 [PNG_RLE_TABLE_WORDS] (codes <= 14 bits, length symbols, header)"""
+        import numpy as np
+        h = np.ascontiguousarray(np.asarray(hist, dtype=np.int64).reshape(-1).astype(np.uint32))
+        assert h.size == 286
+        table = np.zeros(HipOps.PNG_RLE_TABLE_WORDS, dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        check(_L.pf_png_rle_build_table(h.ctypes.data_as(u32p), table.ctypes.data_as(u32p)), "pf_png_rle_build_table")
+        return table
+
+    @staticmethod
+    def png_rle_encode(image, table, workspace, out, meta, bgr=False):
+        """pass B' + C: png_encode with the table of png_rle_build_table (int32 [PNG_RLE_TABLE_WORDS], device)"""
+        H, W, ch, bits, bgr = HipOps.png_format(image, bgr)
+        assert table.dtype == torch.int32 and table.numel() == HipOps.PNG_RLE_TABLE_WORDS and table.is_contiguous()
+        ws_bytes, out_bytes, nbands = HipOps.png_rle_workspace(image)
+        assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.numel() >= ws_bytes
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= out_bytes
+        assert meta.dtype == torch.int32 and meta.is_contiguous() and meta.numel() >= 2 + 3 * nbands
+        check(_L.pf_png_rle_encode(_p(image), H, W, ch, bits, bgr, _p(table), _p(workspace), _p(out), _p(meta), _stream()), "pf_png_rle_encode")
+        return out, meta
+
 
 ops = HipOps()

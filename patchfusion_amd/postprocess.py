@@ -154,24 +154,55 @@ def _png_chunk(kind, data):
     return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(data, zlib.crc32(kind)))
 
 
-def encode_png(image, bgr=False, ops=None):
+PNG_STRATEGIES = ("huffman", "rle", "auto")
+
+
+def png_cost_bits(counts, table, nsym, header_bits, nbands, extra_bits=0):
+    """Exact size in bits of the deflate blocks a table gives: sum of count * code length, the matches' extra bits and one distance
+    bit each (symbols from 257 up), and per band the header, the end-of-block (in counts) and the empty stored block of the flush."""
+    bits = sum(int(c) * (int(t) >> 16) for c, t in zip(counts[:nsym], table[:nsym]))
+    return bits + int(extra_bits) + sum(int(c) for c in counts[257:nsym]) + nbands * (int(header_bits) + 3 + 32)
+
+
+def encode_png(image, bgr=False, strategy="huffman", ops=None):
     """A device image -> the bytes of a PNG file.  image: uint8 [H,W], [H,W,3], [H,W,4] (grey, RGB, RGBA) or torch.uint16 [H,W];
     bgr=True reads channels 0 and 2 swapped, so `colorize(..., layout='bgr')` (the array cv2.imwrite takes, tester.py:69-72) gives the
     file cv2 writes.  Row filters, histogram, Huffman coding and compaction run on the device (csrc/png.hip); the host builds the code
     table from 257 counts (1 KB down, 1.3 KB up), reads the band sizes and Adler-32 partial sums (12 bytes per band of 8 rows) and the
-    compressed bytes, combines the Adler-32 and computes the chunk CRC-32s over the compressed bytes: container checksums, not compute."""
+    compressed bytes, combines the Adler-32 and computes the chunk CRC-32s over the compressed bytes: container checksums, not compute.
+    strategy: 'huffman' codes every filtered byte as a literal; 'rle' adds matches at distance 1 for runs of equal bytes inside a row
+    (csrc/png_rle.hip: smaller colour files, larger 16-bit ones); 'auto' builds both tables from one histogram download and encodes
+    with the one whose exact bit cost is smaller (a tie goes to 'huffman')."""
+    if strategy not in PNG_STRATEGIES:
+        raise ValueError(f"png: strategy must be one of {PNG_STRATEGIES}, got {strategy!r}")
     ops = ops or _ops()
     img = image.detach().contiguous()
     H, W, ch, bits, _ = ops.png_format(img, bgr)
-    ws_bytes, out_bytes, nbands = ops.png_workspace(img, bgr)
     dev = img.device
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    hist = torch.empty(257, dtype=torch.int32, device=dev)
-    ops.png_filter_histogram(img, ws, hist, bgr)
-    table = ops.png_build_table(hist.cpu().numpy().view(np.uint32))
+    if strategy == "huffman":
+        ws_bytes, out_bytes, nbands = ops.png_workspace(img, bgr)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        hist = torch.empty(257, dtype=torch.int32, device=dev)
+        ops.png_filter_histogram(img, ws, hist, bgr)
+        table = ops.png_build_table(hist.cpu().numpy().view(np.uint32))
+        encode = ops.png_encode
+    else:
+        ws_bytes, out_bytes, nbands = ops.png_rle_workspace(img, bgr)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        hist = torch.empty(ops.PNG_RLE_HIST_WORDS, dtype=torch.int32, device=dev)
+        ops.png_rle_filter_histogram(img, ws, hist, bgr)
+        h = hist.cpu().numpy().view(np.uint32)
+        tokens = h[257:257 + 286]
+        table = ops.png_rle_build_table(tokens)
+        encode = ops.png_rle_encode
+        if strategy == "auto":
+            literal_table = ops.png_build_table(h[:257])
+            rle_bits = png_cost_bits(tokens, table, 286, table[286], nbands, int(h[544]) | (int(h[545]) << 32))
+            if png_cost_bits(h[:257], literal_table, 257, literal_table[257], nbands) <= rle_bits:
+                table, encode = literal_table, ops.png_encode
     out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
     meta = torch.empty(2 + 3 * nbands, dtype=torch.int32, device=dev)
-    ops.png_encode(img, torch.from_numpy(table.view(np.int32)).to(dev), ws, out, meta, bgr)
+    encode(img, torch.from_numpy(table.view(np.int32)).to(dev), ws, out, meta, bgr)
     m = meta.cpu().numpy().view(np.uint32).tolist()
     total = m[0] | (m[1] << 32)
     assert total == sum(m[2::3]) and total <= out_bytes, (total, out_bytes)
@@ -187,17 +218,18 @@ def encode_png(image, bgr=False, ops=None):
     return b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", ihdr) + _png_chunk(b"IDAT", idat) + _png_chunk(b"IEND", b"")
 
 
-def save_prediction(result, work_dir, basename, gray_scale=False, ops=None):
+def save_prediction(result, work_dir, basename, gray_scale=False, ops=None, png_strategy="huffman"):
     """tester.py:66-76 with both encodes on the device: `{basename}.png` decodes to colorize(result, cmap='magma_r' | 'gray_r')[..., :3]
-    (what cv2.imwrite makes of the BGR array) and `{basename}_uint16.png` to (depth * 256).astype('uint16').  -> the two paths."""
+    (what cv2.imwrite makes of the BGR array) and `{basename}_uint16.png` to (depth * 256).astype('uint16').  png_strategy is
+    encode_png's `strategy` for both files ('auto' picks per file).  -> the two paths."""
     ops = ops or _ops()
     colour = colorize(result, cmap="gray_r" if gray_scale else "magma_r", ops=ops, layout="bgr")
     colour_path = os.path.join(work_dir, f"{basename}.png")
     uint16_path = os.path.join(work_dir, f"{basename}_uint16.png")
     with open(colour_path, "wb") as f:
-        f.write(encode_png(colour, bgr=True, ops=ops))
+        f.write(encode_png(colour, bgr=True, strategy=png_strategy, ops=ops))
     with open(uint16_path, "wb") as f:
-        f.write(encode_png(depth_to_uint16(result, ops=ops), ops=ops))
+        f.write(encode_png(depth_to_uint16(result, ops=ops), strategy=png_strategy, ops=ops))
     return colour_path, uint16_path
 
 
