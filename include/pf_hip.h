@@ -494,6 +494,78 @@ int pf_png_rle_build_table(const uint32_t* hist286, uint32_t* table);
 int pf_png_rle_encode(const void* img, int H, int W, int channels, int bits, int bgr, const uint32_t* table, void* workspace,
                       uint8_t* out, uint32_t* meta, void* stream);
 
+/* ---- JPEG decoding of the input image (csrc/jpeg.hip, csrc/jpeg_host.h): estimator/datasets/general_dataset.py:27,40 ---- */
+
+/* A baseline JPEG file (SOF0, or SOF1 at 8 bits; one interleaved Huffman scan; grey, or YCbCr at 4:4:4, 4:2:2 or 4:2:0; optional restart
+ * intervals) becomes a device image uint8 [H'][W'][3], RGB, bit-exact with libjpeg's defaults (islow inverse DCT, fancy upsampling).
+ * Between the two halves lies the coefficient array: int16 [nblocks][64], natural (de-zigzagged) order, not dequantised, blocks in MCU
+ * order and in scan order inside an MCU, DC absolute.  Both entropy paths (steps 3 and 6) fill it identically.  Steps:
+ *   1. pf_jpeg_parse: HOST ONLY.  Markers up to the scan -> header.  Every refusal has its own PF_JPEG_E_* code.
+ *   2. pf_jpeg_prepare_scan: HOST ONLY.  scan (capacity >= len - header.scan_begin + 68) receives the entropy-coded bytes with FF 00 ->
+ *      FF and the RSTn markers removed, zero-padded by >= 64 bytes to a multiple of 4 (*scan_bytes, padding included); segs = {first
+ *      bit, end bit} of each of the header.nsegments restart intervals.  Missing EOI, a foreign marker, RSTn out of sequence or count: error.
+ *   3. pf_jpeg_decode_entropy_host: HOST ONLY.  The sequential entropy decoder: scan + segs -> coef (host).  The exact comparator of step 6.
+ *   4. pf_jpeg_plan: HOST ONLY.  Cuts every segment into subsequences ("lanes") of subsequence_bits (a multiple of 32, 32 .. 2^20); lanes
+ *      (null = count only; 3 words per lane: start bit, end bit, segment), segx (4 words per segment: end bit, first lane, first block,
+ *      blocks), *nlanes, *longest = the most lanes one segment has.  pf_jpeg_build_tables: HOST ONLY, header -> PF_JPEG_TABLE_WORDS words.
+ *   5. pf_jpeg_workspace_bytes: the device workspaces of steps 6 and 7.
+ *   6. pf_jpeg_decode_entropy: scan, lanes, segx, tables, workspace and coef on the device (workspace and coef 16-byte aligned, scan 4-byte).
+ *      Decodes every lane from a guessed state, re-decodes from the neighbour's exit state until a round changes nothing (*sync_rounds
+ *      rounds; more than max_sync_rounds needed: PF_JPEG_NOT_CONVERGED, nothing usable in coef), writes the coefficients and makes the DCs
+ *      absolute.  Synchronises the stream once per round (a launch, a 4-byte copy back and a wait) and once at the end.  A broken stream:
+ *      PF_JPEG_E_STREAM.  PF_JPEG_NOT_CONVERGED returns without a final synchronise: kernels of the rounds so far may still be queued, so
+ *      scan, lanes, segx, tables, workspace and coef must be released in stream order (as torch's caching allocator does) or after a
+ *      synchronise.
+ *   7. pf_jpeg_reconstruct: coef (device) -> rgb (device, H x W x 3, or W x H x 3 for orientations 5 .. 8): dequantisation, inverse DCT,
+ *      upsampling, colour transform; the EXIF orientation (1 .. 8; pass 1 to ignore it) is applied in the store address. */
+#define PF_JPEG_TABLE_WORDS 2152
+#define PF_JPEG_E_NOT_JPEG 32
+#define PF_JPEG_E_TRUNCATED 33
+#define PF_JPEG_E_PROGRESSIVE 34
+#define PF_JPEG_E_ARITHMETIC 35
+#define PF_JPEG_E_LOSSLESS 36
+#define PF_JPEG_E_PRECISION 37    /* 12-bit samples */
+#define PF_JPEG_E_QUANT16 38      /* 16-bit quantisation table */
+#define PF_JPEG_E_COMPONENTS 39   /* not 1 or 3 components */
+#define PF_JPEG_E_COLORSPACE 40   /* Adobe transform other than YCbCr, or RGB component ids */
+#define PF_JPEG_E_SAMPLING 41
+#define PF_JPEG_E_MULTISCAN 42
+#define PF_JPEG_E_DNL 43          /* DNL marker, or a height of 0 */
+#define PF_JPEG_E_MARKER 44       /* a marker where none may stand */
+#define PF_JPEG_E_RESTART 45      /* RSTn out of sequence or count */
+#define PF_JPEG_E_NO_EOI 46
+#define PF_JPEG_E_TABLE 47        /* missing or invalid Huffman / quantisation table */
+#define PF_JPEG_E_STREAM 48       /* entropy-coded data does not decode to the frame */
+#define PF_JPEG_E_SCAN 49         /* scan header other than one full sequential scan */
+#define PF_JPEG_NOT_CONVERGED 64
+struct pf_jpeg_header {
+  int32_t width, height, ncomp, hmax, vmax;
+  int32_t restart_interval;       /* MCUs, 0 = none */
+  int32_t orientation;            /* EXIF 1..8 (1 when absent or out of range) */
+  int32_t scan_begin;             /* byte offset of the first entropy-coded byte */
+  int32_t mcus_x, mcus_y, blocks_per_mcu, nblocks, nsegments;
+  int32_t sof;                    /* 0 (SOF0) or 1 (SOF1) */
+  int32_t comp_id[4], comp_h[4], comp_v[4], comp_tq[4], comp_td[4], comp_ta[4];   /* h, v as decoded (1 x 1 for a single component) */
+  uint8_t qt[4][64];              /* natural order */
+  uint8_t qt_present[4];
+  uint8_t huff_bits[8][17];       /* [class * 4 + id][code length], class 0 = DC, 1 = AC */
+  uint8_t huff_vals[8][256];
+  uint8_t huff_present[8];
+};
+typedef struct pf_jpeg_header pf_jpeg_header;
+int pf_jpeg_parse(const uint8_t* data, long len, pf_jpeg_header* header);
+int pf_jpeg_prepare_scan(const uint8_t* data, long len, const pf_jpeg_header* header, uint8_t* scan, long scan_capacity, long* scan_bytes,
+                         uint32_t* segs);
+int pf_jpeg_decode_entropy_host(const pf_jpeg_header* header, const uint8_t* scan, long scan_bytes, const uint32_t* segs, int16_t* coef);
+int pf_jpeg_plan(const pf_jpeg_header* header, const uint32_t* segs, int subsequence_bits, uint32_t* lanes, long lane_capacity,
+                 uint32_t* segx, int* nlanes, int* longest);
+int pf_jpeg_build_tables(const pf_jpeg_header* header, uint32_t* tables);
+int pf_jpeg_workspace_bytes(const pf_jpeg_header* header, int nlanes, long* entropy_bytes, long* recon_bytes);
+int pf_jpeg_decode_entropy(const pf_jpeg_header* header, const uint8_t* scan, long scan_bytes, const uint32_t* lanes, const uint32_t* segx,
+                           int nlanes, int longest, const uint32_t* tables, int max_sync_rounds, void* workspace, int16_t* coef,
+                           int* sync_rounds, void* stream);
+int pf_jpeg_reconstruct(const pf_jpeg_header* header, const int16_t* coef, int orientation, void* workspace, uint8_t* rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,15 @@ class ConvParams(C.Structure):
     ]
 
 
+class JpegHeader(C.Structure):
+    """struct pf_jpeg_header of include/pf_hip.h"""
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "ncomp", "hmax", "vmax", "restart_interval", "orientation", "scan_begin", "mcus_x",
+                                         "mcus_y", "blocks_per_mcu", "nblocks", "nsegments", "sof")] + \
+               [(n, C.c_int32 * 4) for n in ("comp_id", "comp_h", "comp_v", "comp_tq", "comp_td", "comp_ta")] + \
+               [("qt", (C.c_uint8 * 64) * 4), ("qt_present", C.c_uint8 * 4), ("huff_bits", (C.c_uint8 * 17) * 8),
+                ("huff_vals", (C.c_uint8 * 256) * 8), ("huff_present", C.c_uint8 * 8)]
+
+
 # name -> argtypes (every function returns int status except pf_last_error / pf_version)
 SIGNATURES = {
     "pf_conv": [C.POINTER(ConvParams), vp],
@@ -119,6 +128,15 @@ SIGNATURES = {
     "pf_png_rle_filter_histogram": [vp, ci, ci, ci, ci, ci, vp, vp, vp],
     "pf_png_rle_build_table": [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
     "pf_png_rle_encode": [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp],
+    # JPEG decoding of the input image (jpeg.hip); parse, prepare_scan, decode_entropy_host, plan and build_tables are host-only
+    "pf_jpeg_parse": [vp, cl, C.POINTER(JpegHeader)],
+    "pf_jpeg_prepare_scan": [vp, cl, C.POINTER(JpegHeader), vp, cl, C.POINTER(cl), vp],
+    "pf_jpeg_decode_entropy_host": [C.POINTER(JpegHeader), vp, cl, vp, vp],
+    "pf_jpeg_plan": [C.POINTER(JpegHeader), vp, ci, vp, cl, vp, C.POINTER(ci), C.POINTER(ci)],
+    "pf_jpeg_build_tables": [C.POINTER(JpegHeader), vp],
+    "pf_jpeg_workspace_bytes": [C.POINTER(JpegHeader), ci, C.POINTER(cl), C.POINTER(cl)],
+    "pf_jpeg_decode_entropy": [C.POINTER(JpegHeader), vp, cl, vp, vp, ci, ci, vp, ci, vp, vp, C.POINTER(ci), vp],
+    "pf_jpeg_reconstruct": [C.POINTER(JpegHeader), vp, ci, vp, vp, vp],
 }
 NON_STATUS = ("pf_last_error", "pf_version", "pf_percentile_workspace_bytes", "pf_conv_winograd_fused_supported", "pf_gemm_split3_route",
               "pf_gemm_f16x2_points_route", "pf_gemm_f16x2_points_route_ex", "pf_conv_winograd_f16x2_supported_ex",

@@ -1293,5 +1293,42 @@ class HipOps:
         check(_L.pf_png_rle_encode(_p(image), H, W, ch, bits, bgr, _p(table), _p(workspace), _p(out), _p(meta), _stream()), "pf_png_rle_encode")
         return out, meta
 
+    # ---------------- JPEG decoding of the input image (jpeg.hip); the host steps live in preprocess.JpegHost ----------------
+    JPEG_TABLE_WORDS, JPEG_E_STREAM, JPEG_NOT_CONVERGED = 2152, 48, 64     # PF_JPEG_TABLE_WORDS, PF_JPEG_E_STREAM, PF_JPEG_NOT_CONVERGED
+
+    @staticmethod
+    def jpeg_workspace(header, nlanes):
+        """-> (entropy workspace bytes, reconstruction workspace bytes)"""
+        a, b = C.c_long(), C.c_long()
+        check(_L.pf_jpeg_workspace_bytes(C.byref(header), int(nlanes), C.byref(a), C.byref(b)), "pf_jpeg_workspace_bytes")
+        return a.value, b.value
+
+    @staticmethod
+    def jpeg_decode_entropy(header, scan, lanes, segx, longest, tables, max_sync_rounds, workspace, coef):
+        """scan uint8, lanes int32 [nlanes,3], segx int32 [nsegments,4], tables int32, workspace uint8, coef int16 [nblocks,64], all on the
+        device -> (status, sync rounds); status 0, PF_JPEG_E_STREAM or PF_JPEG_NOT_CONVERGED (anything else raises)"""
+        nlanes = int(lanes.shape[0])
+        assert scan.dtype == torch.uint8 and lanes.dtype == torch.int32 and segx.dtype == torch.int32 and tables.dtype == torch.int32
+        assert all(t.is_contiguous() for t in (scan, lanes, segx, tables, workspace, coef))
+        assert coef.dtype == torch.int16 and coef.numel() == header.nblocks * 64 and segx.shape[0] == header.nsegments
+        assert tables.numel() == HipOps.JPEG_TABLE_WORDS
+        assert workspace.dtype == torch.uint8 and workspace.numel() >= HipOps.jpeg_workspace(header, nlanes)[0]
+        rounds = C.c_int()
+        rc = _L.pf_jpeg_decode_entropy(C.byref(header), _p(scan), scan.numel(), _p(lanes), _p(segx), nlanes, int(longest), _p(tables),
+                                       int(max_sync_rounds), _p(workspace), _p(coef), C.byref(rounds), _stream())
+        if rc not in (0, HipOps.JPEG_E_STREAM, HipOps.JPEG_NOT_CONVERGED):
+            check(rc, "pf_jpeg_decode_entropy")
+        return rc, rounds.value
+
+    @staticmethod
+    def jpeg_reconstruct(header, coef, orientation, workspace, rgb):
+        """coef int16 [nblocks,64] -> rgb uint8 [H',W',3] (both on the device)"""
+        H, W = (header.width, header.height) if orientation >= 5 else (header.height, header.width)
+        assert coef.dtype == torch.int16 and coef.is_contiguous() and coef.numel() == header.nblocks * 64
+        assert rgb.dtype == torch.uint8 and rgb.is_contiguous() and tuple(rgb.shape) == (H, W, 3)
+        assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.numel() >= HipOps.jpeg_workspace(header, 0)[1]
+        check(_L.pf_jpeg_reconstruct(C.byref(header), _p(coef), int(orientation), _p(workspace), _p(rgb), _stream()), "pf_jpeg_reconstruct")
+        return rgb
+
 
 ops = HipOps()
