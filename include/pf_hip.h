@@ -544,7 +544,7 @@ struct pf_jpeg_header {
   int32_t orientation;            /* EXIF 1..8 (1 when absent or out of range) */
   int32_t scan_begin;             /* byte offset of the first entropy-coded byte */
   int32_t mcus_x, mcus_y, blocks_per_mcu, nblocks, nsegments;
-  int32_t sof;                    /* 0 (SOF0) or 1 (SOF1) */
+  int32_t sof;                    /* 0 (SOF0) or 1 (SOF1); 2 (SOF2) from pf_jpeg_prog_parse */
   int32_t comp_id[4], comp_h[4], comp_v[4], comp_tq[4], comp_td[4], comp_ta[4];   /* h, v as decoded (1 x 1 for a single component) */
   uint8_t qt[4][64];              /* natural order */
   uint8_t qt_present[4];
@@ -565,6 +565,77 @@ int pf_jpeg_decode_entropy(const pf_jpeg_header* header, const uint8_t* scan, lo
                            int nlanes, int longest, const uint32_t* tables, int max_sync_rounds, void* workspace, int16_t* coef,
                            int* sync_rounds, void* stream);
 int pf_jpeg_reconstruct(const pf_jpeg_header* header, const int16_t* coef, int orientation, void* workspace, uint8_t* rgb, void* stream);
+
+/* ---- progressive JPEG, opt-in (csrc/jpeg_prog.hip, csrc/jpeg_host.h) ----
+ * A progressive file (SOF2, 8 bits, Huffman; colour, sampling and orientation rules as above) fills the same coefficient array, scan by
+ * scan, and is then reconstructed by pf_jpeg_reconstruct.  Only complete progressions are accepted (every coefficient of every component
+ * refined down to bit 0): libjpeg smooths the blocks of an incomplete one.  A scan is interleaved with every component in frame order (DC
+ * scans only), or holds one component; a one-component scan walks that component's own ceil(wc / 8) x ceil(hc / 8) blocks in raster order
+ * (wc = ceil(W * h / hmax)), its restart intervals count those blocks, and a block map turns its block order into the array's MCU order.
+ * Steps, all names carrying the prefix pf_jpeg_prog_:
+ *   1. _parse: HOST ONLY.  The whole file -> the frame header (restart_interval 0, nsegments 1: restart intervals belong to scans) and the
+ *      scan list (capacity: the number of FF DA byte pairs in the file is enough): kind, components, band, Ah, Al, the Huffman tables as
+ *      they stand at that SOS, the byte range of its entropy-coded data and its restart interval.  Progression bookkeeping as libjpeg's
+ *      coef_bits; every refusal has its own PF_JPEG_E_PROG_* code.  A baseline file: PF_JPEG_PROG_BASELINE, nothing else done.
+ *   2. _prepare_scan: HOST ONLY.  As pf_jpeg_prepare_scan for one scan (capacity >= end - begin + 68); segs = scan.nsegments pairs.
+ *   3. _decode_scan_host: HOST ONLY.  The sequential decoder of jdphuff.c for one scan of any kind, applied to coef (host, zeroed by the
+ *      caller before the first scan).  The second entropy path and the exact comparator of steps 6 to 8.
+ *   4. _refine_ac_host: HOST ONLY.  An AC-refinement scan decoded against the non-zero masks of its component's blocks (one uint64 per
+ *      block of the scan, bit k = the coefficient at zigzag position k is non-zero) -> records, three uint64 per block {correction, new, sign of
+ *      new} in the same bit order, and the masks updated.  AC refinement is not self-synchronising, so it has no device decoder.
+ *   5. _plan, _build_tables, _block_map, _workspace_bytes: HOST ONLY.  The subsequence plan and decode tables of one scan (layouts as
+ *      pf_jpeg_plan and pf_jpeg_build_tables; slot 2 * i = DC table of the scan's component i, slot 1 = its AC table), the block map of a
+ *      one-component scan (int32 per block of the scan), and the device workspace of step 6.
+ *   6. _decode_scan: a DC-first or AC-first scan on the device, in the manner of pf_jpeg_decode_entropy (same arguments, status codes and
+ *      synchronisation; map = null for an interleaved scan).  coef is NOT zeroed: the caller zeroes it once before the first scan.
+ *   7. _dc_refine: a DC-refinement scan, one thread per block (segs on the device).
+ *   8. _nonzero_mask: coef -> the masks of step 4 for one component; _apply_refinement: the records of step 4 -> coef. */
+#define PF_JPEG_E_PROG_NO_FIRST 50       /* refinement of a coefficient that had no first scan */
+#define PF_JPEG_E_PROG_AH 51             /* Ah is not the Al of the scan before (or a first scan comes twice) */
+#define PF_JPEG_E_PROG_AL 52             /* a refinement with Al != Ah - 1 */
+#define PF_JPEG_E_PROG_AC_COMPONENTS 53  /* AC scan with more than one component */
+#define PF_JPEG_E_PROG_AC_BEFORE_DC 54   /* AC scan before its component's DC */
+#define PF_JPEG_E_PROG_BAND 55           /* Ss > Se, Se > 63, or a DC scan with Se != 0 */
+#define PF_JPEG_E_PROG_INCOMPLETE 56     /* some coefficient never sent or not refined to bit 0: libjpeg would smooth the file */
+#define PF_JPEG_PROG_BASELINE 65         /* not an error: the file is baseline, use pf_jpeg_parse */
+#define PF_JPEG_PROG_DC_FIRST 0
+#define PF_JPEG_PROG_DC_REFINE 1
+#define PF_JPEG_PROG_AC_FIRST 2
+#define PF_JPEG_PROG_AC_REFINE 3
+struct pf_jpeg_prog_scan {
+  int32_t kind;                   /* PF_JPEG_PROG_DC_FIRST .. PF_JPEG_PROG_AC_REFINE */
+  int32_t ncomp, comp[4];         /* indices into the frame's components, in frame order */
+  int32_t td[4], ta[4];
+  int32_t ss, se, ah, al;
+  int32_t restart_interval;       /* in units of this scan: MCUs when interleaved, blocks otherwise; 0 = none */
+  int32_t begin, end;             /* the scan's entropy-coded bytes in the file: [begin, end), end = the next marker that is not RSTn */
+  int32_t blocks_per_unit, nblocks, nsegments;    /* the scan's own walk */
+  int32_t blocks_x, blocks_y;     /* one-component scan: the component's blocks across and down */
+  uint8_t huff_bits[8][17];       /* the tables as they stand at this SOS, laid out as in pf_jpeg_header */
+  uint8_t huff_vals[8][256];
+};
+typedef struct pf_jpeg_prog_scan pf_jpeg_prog_scan;
+int pf_jpeg_prog_parse(const uint8_t* data, long len, pf_jpeg_header* header, pf_jpeg_prog_scan* scans, int scan_capacity, int* nscans);
+int pf_jpeg_prog_prepare_scan(const uint8_t* data, long len, const pf_jpeg_prog_scan* scan, uint8_t* out, long capacity, long* scan_bytes,
+                              uint32_t* segs);
+int pf_jpeg_prog_decode_scan_host(const pf_jpeg_header* header, const pf_jpeg_prog_scan* scan, const uint8_t* bytes, long scan_bytes,
+                                  const uint32_t* segs, int16_t* coef);
+int pf_jpeg_prog_refine_ac_host(const pf_jpeg_prog_scan* scan, const uint8_t* bytes, long scan_bytes, const uint32_t* segs, uint64_t* masks,
+                                uint64_t* records);
+int pf_jpeg_prog_plan(const pf_jpeg_prog_scan* scan, const uint32_t* segs, int subsequence_bits, uint32_t* lanes, long lane_capacity,
+                      uint32_t* segx, int* nlanes, int* longest);
+int pf_jpeg_prog_build_tables(const pf_jpeg_prog_scan* scan, uint32_t* tables);
+int pf_jpeg_prog_block_map(const pf_jpeg_header* header, const pf_jpeg_prog_scan* scan, int32_t* map);
+int pf_jpeg_prog_workspace_bytes(int nlanes, int scan_blocks, long* bytes);
+int pf_jpeg_prog_decode_scan(const pf_jpeg_header* header, const pf_jpeg_prog_scan* scan, const uint8_t* bytes, long scan_bytes,
+                             const uint32_t* lanes, const uint32_t* segx, int nlanes, int longest, const uint32_t* tables,
+                             const int32_t* map, int max_sync_rounds, void* workspace, int16_t* coef, int* sync_rounds, void* stream);
+int pf_jpeg_prog_dc_refine(const pf_jpeg_header* header, const pf_jpeg_prog_scan* scan, const uint8_t* bytes, long scan_bytes,
+                           const uint32_t* segs, const int32_t* map, int16_t* coef, void* stream);
+int pf_jpeg_prog_nonzero_mask(const pf_jpeg_header* header, const pf_jpeg_prog_scan* scan, const int16_t* coef, const int32_t* map,
+                              uint64_t* masks, void* stream);
+int pf_jpeg_prog_apply_refinement(const pf_jpeg_header* header, const pf_jpeg_prog_scan* scan, const uint64_t* records, const int32_t* map,
+                                  int16_t* coef, void* stream);
 
 #ifdef __cplusplus
 }

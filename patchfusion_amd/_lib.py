@@ -42,6 +42,14 @@ class JpegHeader(C.Structure):
                 ("huff_vals", (C.c_uint8 * 256) * 8), ("huff_present", C.c_uint8 * 8)]
 
 
+class JpegProgScan(C.Structure):
+    """struct pf_jpeg_prog_scan of include/pf_hip.h"""
+    _fields_ = [("kind", C.c_int32), ("ncomp", C.c_int32), ("comp", C.c_int32 * 4), ("td", C.c_int32 * 4), ("ta", C.c_int32 * 4)] + \
+               [(n, C.c_int32) for n in ("ss", "se", "ah", "al", "restart_interval", "begin", "end", "blocks_per_unit", "nblocks", "nsegments",
+                                         "blocks_x", "blocks_y")] + \
+               [("huff_bits", (C.c_uint8 * 17) * 8), ("huff_vals", (C.c_uint8 * 256) * 8)]
+
+
 # name -> argtypes (every function returns int status except pf_last_error / pf_version)
 SIGNATURES = {
     "pf_conv": [C.POINTER(ConvParams), vp],
@@ -137,6 +145,19 @@ SIGNATURES = {
     "pf_jpeg_workspace_bytes": [C.POINTER(JpegHeader), ci, C.POINTER(cl), C.POINTER(cl)],
     "pf_jpeg_decode_entropy": [C.POINTER(JpegHeader), vp, cl, vp, vp, ci, ci, vp, ci, vp, vp, C.POINTER(ci), vp],
     "pf_jpeg_reconstruct": [C.POINTER(JpegHeader), vp, ci, vp, vp, vp],
+    # progressive JPEG (jpeg_prog.hip); decode_scan, dc_refine, nonzero_mask and apply_refinement launch kernels, the rest is host-only
+    "pf_jpeg_prog_parse": [vp, cl, C.POINTER(JpegHeader), C.POINTER(JpegProgScan), ci, C.POINTER(ci)],
+    "pf_jpeg_prog_prepare_scan": [vp, cl, C.POINTER(JpegProgScan), vp, cl, C.POINTER(cl), vp],
+    "pf_jpeg_prog_decode_scan_host": [C.POINTER(JpegHeader), C.POINTER(JpegProgScan), vp, cl, vp, vp],
+    "pf_jpeg_prog_refine_ac_host": [C.POINTER(JpegProgScan), vp, cl, vp, vp, vp],
+    "pf_jpeg_prog_plan": [C.POINTER(JpegProgScan), vp, ci, vp, cl, vp, C.POINTER(ci), C.POINTER(ci)],
+    "pf_jpeg_prog_build_tables": [C.POINTER(JpegProgScan), vp],
+    "pf_jpeg_prog_block_map": [C.POINTER(JpegHeader), C.POINTER(JpegProgScan), vp],
+    "pf_jpeg_prog_workspace_bytes": [ci, ci, C.POINTER(cl)],
+    "pf_jpeg_prog_decode_scan": [C.POINTER(JpegHeader), C.POINTER(JpegProgScan), vp, cl, vp, vp, ci, ci, vp, vp, ci, vp, vp, C.POINTER(ci), vp],
+    "pf_jpeg_prog_dc_refine": [C.POINTER(JpegHeader), C.POINTER(JpegProgScan), vp, cl, vp, vp, vp, vp],
+    "pf_jpeg_prog_nonzero_mask": [C.POINTER(JpegHeader), C.POINTER(JpegProgScan), vp, vp, vp, vp],
+    "pf_jpeg_prog_apply_refinement": [C.POINTER(JpegHeader), C.POINTER(JpegProgScan), vp, vp, vp, vp],
 }
 NON_STATUS = ("pf_last_error", "pf_version", "pf_percentile_workspace_bytes", "pf_conv_winograd_fused_supported", "pf_gemm_split3_route",
               "pf_gemm_f16x2_points_route", "pf_gemm_f16x2_points_route_ex", "pf_conv_winograd_f16x2_supported_ex",

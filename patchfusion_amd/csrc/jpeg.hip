@@ -20,15 +20,11 @@
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
 #include "jpeg_host.h"
+#include "jpeg_dev.h"
 
 namespace {
 
 using namespace pf_jpeg;
-
-inline int ok() { return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH; }
-#define ST(s) reinterpret_cast<hipStream_t>(s)
-
-constexpr int JT = 256;                      // threads per block of every kernel here
 
 // exit state of a lane in one word, so that a lane reads its neighbour's state whole: p | k << 32 | b << 39 | blocks << 42
 __device__ __forceinline__ unsigned long long pack_state(uint32_t p, int b, int k, uint32_t n) {
@@ -183,28 +179,6 @@ struct DcGeom {
   int nblocks, bpm, segblocks;      // segblocks = restart interval * bpm, or nblocks without restart intervals
   uint32_t comp_of;
 };
-struct Dc4 { int f, v0, v1, v2; };
-__device__ __forceinline__ Dc4 dc_combine(const Dc4& a, const Dc4& b) {     // a before b
-  Dc4 r;
-  r.f = a.f | b.f;
-  r.v0 = b.f ? b.v0 : a.v0 + b.v0;
-  r.v1 = b.f ? b.v1 : a.v1 + b.v1;
-  r.v2 = b.f ? b.v2 : a.v2 + b.v2;
-  return r;
-}
-__device__ __forceinline__ Dc4 dc_block_scan(Dc4 x, Dc4* sh) {              // inclusive, over the JT threads of a block
-  const int t = threadIdx.x;
-  sh[t] = x;
-  __syncthreads();
-  for (int o = 1; o < JT; o <<= 1) {
-    Dc4 y = x;
-    if (t >= o) y = dc_combine(sh[t - o], x);
-    __syncthreads();
-    sh[t] = x = y;
-    __syncthreads();
-  }
-  return x;
-}
 __device__ __forceinline__ Dc4 dc_element(const DcGeom& g, const int16_t* __restrict__ coef, int j) {
   Dc4 x = {0, 0, 0, 0};
   if (j < g.nblocks) {
@@ -226,22 +200,6 @@ __global__ __launch_bounds__(JT) void jpeg_dc_partial_kernel(DcGeom g, const int
     local[j] = c == 0 ? x.v0 : (c == 1 ? x.v1 : x.v2);
   }
   if (threadIdx.x == JT - 1) agg[blockIdx.x] = x;
-}
-// exclusive scan of the chunk aggregates, in place (one block; a run of chunks per thread)
-__global__ __launch_bounds__(JT) void jpeg_dc_carry_kernel(Dc4* __restrict__ agg, int nchunks) {
-  __shared__ Dc4 sh[JT];
-  const int t = threadIdx.x, per = (nchunks + JT - 1) / JT;
-  const int a = min(t * per, nchunks), e = min(a + per, nchunks);
-  Dc4 sum = {0, 0, 0, 0};
-  for (int i = a; i < e; ++i) sum = dc_combine(sum, agg[i]);
-  dc_block_scan(sum, sh);
-  Dc4 run = {0, 0, 0, 0};
-  if (t > 0) run = sh[t - 1];
-  for (int i = a; i < e; ++i) {
-    const Dc4 x = agg[i];
-    agg[i] = run;
-    run = dc_combine(run, x);
-  }
 }
 __global__ __launch_bounds__(JT) void jpeg_dc_apply_kernel(DcGeom g, const int* __restrict__ local, const Dc4* __restrict__ carry, int16_t* __restrict__ coef) {
   const int j = blockIdx.x * JT + threadIdx.x;

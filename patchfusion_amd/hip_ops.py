@@ -1330,5 +1330,59 @@ class HipOps:
         check(_L.pf_jpeg_reconstruct(C.byref(header), _p(coef), int(orientation), _p(workspace), _p(rgb), _stream()), "pf_jpeg_reconstruct")
         return rgb
 
+    # ---------------- progressive JPEG (jpeg_prog.hip); the host steps live in preprocess.JpegProgHost ----------------
+    @staticmethod
+    def jpeg_prog_workspace(nlanes, scan_blocks):
+        n = C.c_long()
+        check(_L.pf_jpeg_prog_workspace_bytes(int(nlanes), int(scan_blocks), C.byref(n)), "pf_jpeg_prog_workspace_bytes")
+        return n.value
+
+    @staticmethod
+    def jpeg_prog_decode_scan(header, scan, data, lanes, segx, longest, tables, block_map, max_sync_rounds, workspace, coef):
+        """a DC-first or AC-first scan: data uint8, lanes int32 [nlanes,3], segx int32 [nsegments,4], tables int32, block_map int32 [scan
+        blocks] or None (interleaved scan), workspace uint8, coef int16 [nblocks,64] (not zeroed here), all on the device -> (status,
+        sync rounds); status 0, PF_JPEG_E_STREAM or PF_JPEG_NOT_CONVERGED (anything else raises)"""
+        nlanes = int(lanes.shape[0])
+        assert data.dtype == torch.uint8 and lanes.dtype == torch.int32 and segx.dtype == torch.int32 and tables.dtype == torch.int32
+        assert all(t.is_contiguous() for t in (data, lanes, segx, tables, workspace, coef))
+        assert coef.dtype == torch.int16 and coef.numel() == header.nblocks * 64 and segx.shape[0] == scan.nsegments
+        assert tables.numel() == HipOps.JPEG_TABLE_WORDS
+        assert block_map is None or (block_map.dtype == torch.int32 and block_map.is_contiguous() and block_map.numel() == scan.nblocks)
+        assert workspace.dtype == torch.uint8 and workspace.numel() >= HipOps.jpeg_prog_workspace(nlanes, scan.nblocks)
+        rounds = C.c_int()
+        rc = _L.pf_jpeg_prog_decode_scan(C.byref(header), C.byref(scan), _p(data), data.numel(), _p(lanes), _p(segx), nlanes, int(longest),
+                                         _p(tables), None if block_map is None else _p(block_map), int(max_sync_rounds), _p(workspace), _p(coef),
+                                         C.byref(rounds), _stream())
+        if rc not in (0, HipOps.JPEG_E_STREAM, HipOps.JPEG_NOT_CONVERGED):
+            check(rc, "pf_jpeg_prog_decode_scan")
+        return rc, rounds.value
+
+    @staticmethod
+    def jpeg_prog_dc_refine(header, scan, data, segs, block_map, coef):
+        """a DC-refinement scan: data uint8, segs int32 [nsegments,2] on the device"""
+        assert data.dtype == torch.uint8 and data.is_contiguous() and segs.dtype == torch.int32 and segs.is_contiguous()
+        assert segs.numel() == 2 * scan.nsegments and coef.dtype == torch.int16 and coef.is_contiguous() and coef.numel() == header.nblocks * 64
+        assert block_map is None or (block_map.dtype == torch.int32 and block_map.is_contiguous() and block_map.numel() == scan.nblocks)
+        check(_L.pf_jpeg_prog_dc_refine(C.byref(header), C.byref(scan), _p(data), data.numel(), _p(segs), None if block_map is None else _p(block_map),
+                                        _p(coef), _stream()), "pf_jpeg_prog_dc_refine")
+
+    @staticmethod
+    def jpeg_prog_nonzero_mask(header, scan, coef, block_map, masks):
+        """coef -> masks int64 [scan blocks] (device): bit i = coefficient i of the block is non-zero"""
+        assert coef.dtype == torch.int16 and coef.is_contiguous() and coef.numel() == header.nblocks * 64
+        assert masks.dtype == torch.int64 and masks.is_contiguous() and masks.numel() == scan.nblocks
+        assert block_map.dtype == torch.int32 and block_map.is_contiguous() and block_map.numel() == scan.nblocks
+        check(_L.pf_jpeg_prog_nonzero_mask(C.byref(header), C.byref(scan), _p(coef), _p(block_map), _p(masks), _stream()), "pf_jpeg_prog_nonzero_mask")
+        return masks
+
+    @staticmethod
+    def jpeg_prog_apply_refinement(header, scan, records, block_map, coef):
+        """records int64 [scan blocks,3] (device) of an AC-refinement scan -> coef"""
+        assert coef.dtype == torch.int16 and coef.is_contiguous() and coef.numel() == header.nblocks * 64
+        assert records.dtype == torch.int64 and records.is_contiguous() and records.numel() == 3 * scan.nblocks
+        assert block_map.dtype == torch.int32 and block_map.is_contiguous() and block_map.numel() == scan.nblocks
+        check(_L.pf_jpeg_prog_apply_refinement(C.byref(header), C.byref(scan), _p(records), _p(block_map), _p(coef), _stream()),
+              "pf_jpeg_prog_apply_refinement")
+
 
 ops = HipOps()

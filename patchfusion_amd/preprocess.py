@@ -20,11 +20,16 @@ from . import _lib
 # device entropy path takes 2.5 ms at 1024-bit subsequences (3.5 ms at 256, 3.3 ms at 4096) against 35.2 ms for the host entropy path and
 # 40.7 ms for PIL + upload, so the device path and 1024 bits are the defaults.  The round cap is four times the largest round count seen at
 # 1024 bits on those files (12) and on the fixture (121, the 256x256 q100 noise file, which never self-synchronises).
+# Progressive files (progressive=True; tools/jpeg_prog_decode_time.py, profiles/jpeg_prog_decode_time.json) keep both defaults: 256 and 1024
+# bits are within 6 % of each other there with no consistent order (36.9 ms at 1024 bits at 3840x2160 against 73.2 ms for PIL + upload and
+# 62.2 ms for the host entropy path), 4096 is slower on every file, and the host's AC refinement, not the rounds, is 73-89 % of the time.
 JPEG_SUBSEQUENCE_BITS = 1024
 JPEG_MAX_SYNC_ROUNDS = 484
 
 
 JPEG_TABLE_WORDS, JPEG_E_STREAM, JPEG_NOT_CONVERGED = 2152, 48, 64      # PF_JPEG_TABLE_WORDS, PF_JPEG_E_STREAM, PF_JPEG_NOT_CONVERGED of pf_hip.h
+JPEG_PROG_BASELINE = 65                                                 # PF_JPEG_PROG_BASELINE
+JPEG_PROG_KINDS = ("dc_first", "dc_refine", "ac_first", "ac_refine")    # PF_JPEG_PROG_DC_FIRST .. PF_JPEG_PROG_AC_REFINE
 
 
 class JpegError(ValueError):
@@ -58,6 +63,15 @@ JPEG_ERRORS = {
     47: _refusal("JpegTable", "missing or invalid Huffman or quantisation table"),
     JPEG_E_STREAM: _refusal("JpegStream", "the entropy-coded data does not decode to the frame"),
     49: _refusal("JpegScan", "the scan header is not one full sequential scan"),
+    # progressive files (decode_jpeg(..., progressive=True))
+    50: _refusal("JpegProgNoFirst", "progressive: a scan refines a coefficient that had no first scan"),
+    51: _refusal("JpegProgAh", "progressive: a scan's Ah is not the Al the coefficient was last sent at"),
+    52: _refusal("JpegProgAl", "progressive: a refinement scan with Al other than Ah - 1"),
+    53: _refusal("JpegProgAcComponents", "progressive: an AC scan with more than one component"),
+    54: _refusal("JpegProgAcBeforeDc", "progressive: an AC scan before its component's DC scan"),
+    55: _refusal("JpegProgBand", "progressive: a scan's band is not Ss <= Se <= 63 (Se = 0 for a DC scan)"),
+    56: _refusal("JpegProgIncomplete", "progressive: the progression is incomplete (a coefficient never sent, or not refined to bit 0); "
+                                       "libjpeg would smooth such a file, which is not reproduced"),
 }
 
 
@@ -123,6 +137,166 @@ class JpegHost:
         return t
 
 
+class JpegProgHost:
+    """the HOST ONLY steps of the progressive decoder (csrc/jpeg_host.h through the C ABI): no GPU call.  .baseline is True for a baseline
+    file (nothing else is set then: use JpegHost)."""
+
+    def __init__(self, data):
+        self.lib = _lib.load()
+        raw = bytes(data)
+        self.data = np.frombuffer(raw, dtype=np.uint8)
+        self.header = _lib.JpegHeader()
+        cap = raw.count(b"\xff\xda") + 1                     # every SOS is such a pair
+        arr = (_lib.JpegProgScan * cap)()
+        n = C.c_int()
+        rc = self.lib.pf_jpeg_prog_parse(self.data.ctypes.data, self.data.size, C.byref(self.header), arr, cap, C.byref(n))
+        self.baseline = rc == JPEG_PROG_BASELINE
+        if not self.baseline:
+            _jpeg_check(rc, "pf_jpeg_prog_parse")
+        self.scans = [arr[i] for i in range(n.value)]
+        self._keep = arr
+
+    def prepare(self, scan):
+        """-> (the scan's unstuffed bytes, zero-padded; segs uint32 [nsegments, 2])"""
+        cap = scan.end - scan.begin + 68
+        out = np.zeros(cap, dtype=np.uint8)
+        segs = np.zeros((scan.nsegments, 2), dtype=np.uint32)
+        n = C.c_long()
+        _jpeg_check(self.lib.pf_jpeg_prog_prepare_scan(self.data.ctypes.data, self.data.size, C.byref(scan), out.ctypes.data, cap, C.byref(n),
+                                                       segs.ctypes.data), "pf_jpeg_prog_prepare_scan")
+        return out[:n.value], segs
+
+    def decode_scan(self, scan, coef, prepared=None):
+        """the sequential decoder of one scan applied to coef int16 [nblocks, 64]"""
+        data, segs = prepared or self.prepare(scan)
+        _jpeg_check(self.lib.pf_jpeg_prog_decode_scan_host(C.byref(self.header), C.byref(scan), data.ctypes.data, data.size, segs.ctypes.data,
+                                                           coef.ctypes.data), "pf_jpeg_prog_decode_scan_host")
+
+    def decode_entropy(self):
+        """every scan through the sequential decoder -> int16 [nblocks, 64]"""
+        coef = np.zeros((self.header.nblocks, 64), dtype=np.int16)
+        for scan in self.scans:
+            self.decode_scan(scan, coef)
+        return coef
+
+    def refine_ac(self, scan, masks, prepared=None):
+        """an AC-refinement scan against masks uint64 [scan blocks] (updated in place) -> records uint64 [scan blocks, 3]"""
+        data, segs = prepared or self.prepare(scan)
+        assert masks.dtype == np.uint64 and masks.flags.c_contiguous and masks.size == scan.nblocks
+        rec = np.zeros((scan.nblocks, 3), dtype=np.uint64)
+        _jpeg_check(self.lib.pf_jpeg_prog_refine_ac_host(C.byref(scan), data.ctypes.data, data.size, segs.ctypes.data, masks.ctypes.data,
+                                                         rec.ctypes.data), "pf_jpeg_prog_refine_ac_host")
+        return rec
+
+    def plan(self, scan, segs, subsequence_bits):
+        nl, longest = C.c_int(), C.c_int()
+        S = int(subsequence_bits)
+        _jpeg_check(self.lib.pf_jpeg_prog_plan(C.byref(scan), segs.ctypes.data, S, None, 0, None, C.byref(nl), C.byref(longest)), "pf_jpeg_prog_plan")
+        lanes = np.zeros((nl.value, 3), dtype=np.uint32)
+        segx = np.zeros((scan.nsegments, 4), dtype=np.uint32)
+        _jpeg_check(self.lib.pf_jpeg_prog_plan(C.byref(scan), segs.ctypes.data, S, lanes.ctypes.data, nl.value, segx.ctypes.data, C.byref(nl),
+                                               C.byref(longest)), "pf_jpeg_prog_plan")
+        return lanes, segx, longest.value
+
+    def tables(self, scan):
+        t = np.zeros(JPEG_TABLE_WORDS, dtype=np.uint32)
+        _jpeg_check(self.lib.pf_jpeg_prog_build_tables(C.byref(scan), t.ctypes.data), "pf_jpeg_prog_build_tables")
+        return t
+
+    def block_map(self, scan):
+        """int32 [scan blocks]: where each block of a one-component scan's raster walk lies in the coefficient array"""
+        m = np.zeros(scan.nblocks, dtype=np.int32)
+        _jpeg_check(self.lib.pf_jpeg_prog_block_map(C.byref(self.header), C.byref(scan), m.ctypes.data), "pf_jpeg_prog_block_map")
+        return m
+
+
+def _scan_entry(scan, where, rounds):
+    return dict(kind=JPEG_PROG_KINDS[scan.kind], components=tuple(scan.comp[:scan.ncomp]), band=(scan.ss, scan.se), ah=scan.ah, al=scan.al,
+                bytes=scan.end - scan.begin, decoded=where, sync_rounds=rounds)
+
+
+def jpeg_prog_entropy_device(host, ops, device, subsequence_bits, max_sync_rounds, timing=None):
+    """the scans of a JpegProgHost in file order on one stream -> (status, per-scan entries, coefficients int16 [nblocks,64] on the device,
+    bytes uploaded, bytes downloaded).  DC-first, AC-first and DC-refinement scans are decoded on the device; an AC-refinement scan on the
+    host against the component's non-zero masks (downloaded once per component, again only if an AC-first scan of it ran since) and its
+    records are applied on the device.  status JPEG_NOT_CONVERGED: a scan exceeded max_sync_rounds, nothing usable in the coefficients.
+    timing: a dict that receives the seconds spent in 'device_scans' (with their host preparation and uploads), 'mask_download',
+    'host_refine' (with the scan's preparation), 'record_upload' and 'apply'; each part then ends in a synchronise, which the untimed
+    path does not do."""
+    import time
+    h = host.header
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(device)           # noqa: E731
+    coef = torch.zeros((h.nblocks, 64), dtype=torch.int16, device=device)
+    maps, masks, entries, uploaded, downloaded = {}, {}, [], 0, 0
+
+    def sync():
+        if timing is not None and device.type == "cuda":
+            torch.cuda.synchronize(device)
+
+    def tick(key, t0):
+        if timing is not None:
+            sync()
+            timing[key] = timing.get(key, 0.0) + time.perf_counter() - t0
+
+    def block_map(scan):
+        nonlocal uploaded
+        if scan.ncomp > 1:
+            return None
+        c = scan.comp[0]
+        if c not in maps:
+            m = host.block_map(scan)
+            maps[c] = up(m, np.int32)
+            uploaded += m.nbytes
+        return maps[c]
+
+    for scan in host.scans:
+        sync()
+        t0 = time.perf_counter()
+        data, segs = host.prepare(scan)
+        bmap = block_map(scan)
+        kind = JPEG_PROG_KINDS[scan.kind]
+        if kind in ("dc_first", "ac_first"):
+            lanes, segx, longest = host.plan(scan, segs, subsequence_bits)
+            tables = host.tables(scan)
+            ws = torch.empty(ops.jpeg_prog_workspace(lanes.shape[0], scan.nblocks), dtype=torch.uint8, device=device)
+            rc, rounds = ops.jpeg_prog_decode_scan(h, scan, up(data, np.uint8), up(lanes, np.int32), up(segx, np.int32), longest,
+                                                   up(tables, np.int32), bmap, max_sync_rounds, ws, coef)
+            uploaded += data.nbytes + lanes.nbytes + segx.nbytes + tables.nbytes
+            if rc == JPEG_NOT_CONVERGED:
+                return rc, entries, coef, uploaded, downloaded
+            _jpeg_check(rc, "pf_jpeg_prog_decode_scan")
+            if kind == "ac_first" and scan.comp[0] in masks:
+                masks[scan.comp[0]] = None                       # the component's non-zero map changed on the device
+            entries.append(_scan_entry(scan, "device", rounds))
+            tick("device_scans", t0)
+        elif kind == "dc_refine":
+            ops.jpeg_prog_dc_refine(h, scan, up(data, np.uint8), up(segs, np.int32), bmap, coef)
+            uploaded += data.nbytes + segs.nbytes
+            entries.append(_scan_entry(scan, "device", 0))
+            tick("device_scans", t0)
+        else:
+            c = scan.comp[0]
+            tick("host_refine", t0)
+            if masks.get(c) is None:
+                t0 = time.perf_counter()
+                m = ops.jpeg_prog_nonzero_mask(h, scan, coef, bmap, torch.empty(scan.nblocks, dtype=torch.int64, device=device))
+                masks[c] = np.ascontiguousarray(m.cpu().numpy()).view(np.uint64)
+                downloaded += masks[c].nbytes
+                tick("mask_download", t0)
+            t0 = time.perf_counter()
+            rec = host.refine_ac(scan, masks[c], (data, segs))
+            tick("host_refine", t0)
+            t0 = time.perf_counter()
+            records = up(rec, np.int64)
+            uploaded += rec.nbytes
+            tick("record_upload", t0)
+            t0 = time.perf_counter()
+            ops.jpeg_prog_apply_refinement(h, scan, records, bmap, coef)
+            tick("apply", t0)
+            entries.append(_scan_entry(scan, "host", 0))
+    return 0, entries, coef, uploaded, downloaded
+
+
 def jpeg_entropy_device(host, ops, device, subsequence_bits, max_sync_rounds):
     """the device entropy step of decode_jpeg on a JpegHost -> (status, sync rounds, coefficients int16 [nblocks,64] on the device, bytes
     uploaded); status 0, or JPEG_NOT_CONVERGED with nothing usable in the coefficients (a broken stream raises)"""
@@ -139,12 +313,17 @@ def jpeg_entropy_device(host, ops, device, subsequence_bits, max_sync_rounds):
     return rc, rounds, coef, host.scan.nbytes + lanes.nbytes + segx.nbytes + tables.nbytes
 
 
-def decode_jpeg(data, device="cuda", entropy="device", apply_orientation=True, subsequence_bits=None, max_sync_rounds=None, ops=None):
+def decode_jpeg(data, device="cuda", entropy="device", apply_orientation=True, subsequence_bits=None, max_sync_rounds=None, ops=None,
+                progressive=False):
     """Baseline JPEG (bytes or a path) -> (uint8 [H,W,3] RGB device tensor, JpegInfo), bit-exact with libjpeg's defaults (islow, fancy
     upsampling): what ``cv2.imread`` + BGR->RGB gives (apply_orientation=True) or PIL (False).  entropy='device' uploads the compressed
     scan and decodes it in subsequences on the GPU; 'host' runs the sequential C decoder and uploads the coefficients.
     When the device path needs more than max_sync_rounds rounds the entropy step completes on the host path (info.entropy says so); the
-    pixels are the same either way.  Unsupported files raise a JpegError subclass (a ValueError); there is no fallback to a host library."""
+    pixels are the same either way.  Unsupported files raise a JpegError subclass (a ValueError); there is no fallback to a host library.
+    progressive=True also accepts progressive files (SOF2) with a complete progression, again bit-exact with libjpeg; a baseline file
+    takes the baseline path unchanged.  entropy='device' then decodes the DC-first, AC-first and DC-refinement scans on the GPU and the
+    AC-refinement scans on the host (info.scans says where each scan went); 'host' runs the sequential decoder over every scan.  A scan
+    that exceeds max_sync_rounds completes the whole file on the host path."""
     if entropy not in ("device", "host"):
         raise ValueError(f"entropy must be 'device' or 'host', got {entropy!r}")
     S = JPEG_SUBSEQUENCE_BITS if subsequence_bits is None else int(subsequence_bits)
@@ -162,6 +341,10 @@ def decode_jpeg(data, device="cuda", entropy="device", apply_orientation=True, s
         from .hip_ops import ops as _ops        # fails loudly when the HIP extension is missing
         ops = _ops
     dev = torch.device(device)
+    if progressive:
+        prog = JpegProgHost(data)
+        if not prog.baseline:
+            return _decode_jpeg_progressive(prog, ops, dev, entropy, apply_orientation, S, cap)
     host = JpegHost(data)
     h = host.header
     used, rounds, uploaded, coef = entropy, 0, 0, None
@@ -178,7 +361,32 @@ def decode_jpeg(data, device="cuda", entropy="device", apply_orientation=True, s
     rgb = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
     ops.jpeg_reconstruct(h, coef, o, torch.empty(ops.jpeg_workspace(h, 0)[1], dtype=torch.uint8, device=dev), rgb)
     info = JpegInfo(width=h.width, height=h.height, components=h.ncomp, sampling=(h.hmax, h.vmax), restart_interval=h.restart_interval,
-                    orientation=h.orientation, entropy=used, sync_rounds=rounds, subsequence_bits=S, bytes_uploaded=uploaded)
+                    orientation=h.orientation, entropy=used, sync_rounds=rounds, subsequence_bits=S, bytes_uploaded=uploaded,
+                    progressive=False, scans=[])
+    return rgb, info
+
+
+def _decode_jpeg_progressive(host, ops, dev, entropy, apply_orientation, S, cap):
+    """decode_jpeg for a progressive file (a JpegProgHost that is not baseline)"""
+    h = host.header
+    used, uploaded, downloaded, coef, scans = entropy, 0, 0, None, None
+    if entropy == "device":
+        rc, scans, coef, uploaded, downloaded = jpeg_prog_entropy_device(host, ops, dev, S, cap)
+        if rc == JPEG_NOT_CONVERGED:
+            used = "host"                        # round cap exceeded in some scan: the whole file from the sequential decoder
+    if used == "host":
+        c = host.decode_entropy()
+        uploaded += c.nbytes
+        coef = torch.from_numpy(c).to(dev)
+        scans = [_scan_entry(s, "host", 0) for s in host.scans]
+    o = h.orientation if apply_orientation else 1
+    H, W = (h.width, h.height) if o >= 5 else (h.height, h.width)
+    rgb = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    ops.jpeg_reconstruct(h, coef, o, torch.empty(ops.jpeg_workspace(h, 0)[1], dtype=torch.uint8, device=dev), rgb)
+    info = JpegInfo(width=h.width, height=h.height, components=h.ncomp, sampling=(h.hmax, h.vmax),
+                    restart_interval=max(s.restart_interval for s in host.scans), orientation=h.orientation, entropy=used,
+                    sync_rounds=max(e["sync_rounds"] for e in scans), subsequence_bits=S, bytes_uploaded=uploaded,
+                    bytes_downloaded=downloaded, progressive=True, scans=scans)
     return rgb, info
 
 
