@@ -637,6 +637,76 @@ int pf_jpeg_prog_nonzero_mask(const pf_jpeg_header* header, const pf_jpeg_prog_s
 int pf_jpeg_prog_apply_refinement(const pf_jpeg_header* header, const pf_jpeg_prog_scan* scan, const uint64_t* records, const int32_t* map,
                                   int16_t* coef, void* stream);
 
+/* ---------------------------------------------------------------- PNG decoding of the input image (csrc/png_decode.hip, csrc/png_host.h,
+ * csrc/png_inflate.h).  Non-interlaced files of every colour type and bit depth; the inflate runs on the device:
+ *   1. pf_pngd_parse: HOST ONLY.  Chunk walk, IHDR / PLTE / tRNS validation, the IDAT payloads concatenated behind the zlib header
+ *      (which is checked) into `deflate`.  Every refusal has its own PF_PNGD_E_* code.
+ *      The device (and *_host) steps take the deflate data as little-endian 32-bit `words` with PF_PNGD_PAD_WORDS zero words behind.
+ *   2. pf_pngd_find: one thread per bit offset tests for a well-formed dynamic block header and appends the offset to `list`
+ *      (capacity words); *count keeps counting past the capacity, nothing is written past it.  Offset 0 is listed when a fixed or
+ *      dynamic block starts there.
+ *   3. pf_pngd_scan: one wave per listed start decodes to the end-of-block code without storing; records of four words
+ *      {start bit, end bit, output bytes, status | BFINAL << 8}, status one of PF_PNGD_S_*.
+ *   4. the chain walk is the caller's (preprocess.decode_png): it yields the block table, four words per block
+ *      {start (bit of the header; byte of the data for a stored block), type, output offset, output bytes}.
+ *   5. pf_pngd_inflate: one wave per block writes literals to `lit` and a 32-bit reference per output byte to `ref`.
+ *   6. pf_pngd_resolve: `rounds` pointer-jumping launches, then the gather into `out`.
+ *   7. pf_pngd_unfilter: `inflated` (height rows of 1 + rowbytes) -> `recon` (height rows of rowbytes), exact per the specification.
+ *   8. pf_pngd_expand: `recon` -> the image for the cases whose layout differs from it (sub-byte samples, palette, 16-bit byte order).
+ *   9. pf_pngd_adler: the Adler-32 of `data` into result[0].
+ * `status` (a device word, zeroed by the caller) collects PF_PNGD_F_* flags from steps 5, 7 and 8.  Every device step is ordered on
+ * `stream`; none synchronises.  pf_pngd_find_host, pf_pngd_scan_host and pf_pngd_inflate_model_host are the same code run
+ * sequentially on the host (no GPU call), for tests.
+ * pf_pngd_to_rgb8: any decoded layout -> uint8 [H,W,3]: grey replicated, alpha dropped, 16-bit samples keep their high byte. */
+#define PF_PNGD_E_SIGNATURE 80
+#define PF_PNGD_E_CHUNK 81        /* chunk length, a truncated file, an unknown critical chunk, a bad tRNS */
+#define PF_PNGD_E_ORDER 82        /* chunk order */
+#define PF_PNGD_E_CRC 83          /* CRC of a critical chunk other than IDAT */
+#define PF_PNGD_E_IHDR 84         /* a combination the specification forbids */
+#define PF_PNGD_E_INTERLACED 85   /* Adam7 */
+#define PF_PNGD_E_ZLIB 86         /* zlib header: CM != 8, window > 32 KiB, FDICT, FCHECK */
+#define PF_PNGD_E_STREAM 87       /* invalid or truncated deflate stream */
+#define PF_PNGD_E_DISTANCE 88     /* a match reaches before the start of the output */
+#define PF_PNGD_E_SIZE 89         /* inflated size != height * (1 + rowbytes) */
+#define PF_PNGD_E_ADLER 90
+#define PF_PNGD_E_FILTER 91       /* a row's filter type is above 4 */
+#define PF_PNGD_E_PLTE 92         /* missing or invalid PLTE, or a pixel indexes past it */
+#define PF_PNGD_E_IDAT_CRC 93     /* only with check_idat_crc */
+#define PF_PNGD_PAD_WORDS 2       /* zero words the caller puts behind the deflate data: `words` holds (nbits + 31) / 32 + 2 (nwords says so) */
+#define PF_PNGD_S_OK 0
+#define PF_PNGD_S_INVALID 1
+#define PF_PNGD_S_LIMIT 2         /* max_block_bits reached */
+#define PF_PNGD_S_EOS 3           /* end of the stream reached */
+#define PF_PNGD_S_SIZE 4          /* more output than the image holds */
+#define PF_PNGD_S_DIST 5
+#define PF_PNGD_F_STREAM 1
+#define PF_PNGD_F_DISTANCE 2
+#define PF_PNGD_F_FILTER 4
+#define PF_PNGD_F_PLTE 8
+struct pf_pngd_header {
+  int32_t width, height, depth, color_type, interlace;
+  int32_t channels, bpp;          /* bpp = max(1, channels * depth / 8): the filters' byte distance */
+  int32_t has_trns, plte_entries, idat_chunks;
+  int64_t rowbytes, inflated_bytes, compressed_bytes;   /* inflated_bytes = height * (1 + rowbytes); compressed = the IDAT payloads */
+  uint8_t palette[768];
+};
+typedef struct pf_pngd_header pf_pngd_header;
+int pf_pngd_parse(const uint8_t* data, long len, int check_idat_crc, pf_pngd_header* header, uint8_t* deflate, long capacity, long* deflate_len);
+int pf_pngd_find_host(const uint32_t* words, long nwords, uint32_t nbits, uint32_t* list, long capacity, long* count);
+int pf_pngd_scan_host(const uint32_t* words, long nwords, uint32_t nbits, const uint32_t* starts, int n, uint32_t max_block_bits, uint32_t expected,
+                      uint32_t* records);
+int pf_pngd_inflate_model_host(const uint8_t* deflate, long len, long expected, uint32_t max_block_bits, uint8_t* out, long* stats);
+int pf_pngd_find(const uint32_t* words, long nwords, uint32_t nbits, uint32_t* list, uint32_t capacity, uint32_t* count, void* stream);
+int pf_pngd_scan(const uint32_t* words, long nwords, uint32_t nbits, const uint32_t* starts, int n, uint32_t max_block_bits, uint32_t expected,
+                 uint32_t* records, void* stream);
+int pf_pngd_inflate(const uint32_t* words, long nwords, uint32_t nbits, const uint32_t* blocks, int nblocks, uint32_t expected, uint8_t* lit,
+                    uint32_t* ref, uint32_t* status, void* stream);
+int pf_pngd_resolve(const uint8_t* lit, uint32_t* ref, uint32_t n, int rounds, uint8_t* out, void* stream);
+int pf_pngd_unfilter(const uint8_t* inflated, const pf_pngd_header* header, uint8_t* recon, uint32_t* status, void* stream);
+int pf_pngd_expand(const uint8_t* recon, const pf_pngd_header* header, const uint8_t* palette, void* image, uint32_t* status, void* stream);
+int pf_pngd_adler(const uint8_t* data, long n, uint64_t* sums, uint32_t* result, void* stream);
+int pf_pngd_to_rgb8(const void* image, int height, int width, int channels, int bits, uint8_t* rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,13 @@ class JpegProgScan(C.Structure):
                [("huff_bits", (C.c_uint8 * 17) * 8), ("huff_vals", (C.c_uint8 * 256) * 8)]
 
 
+class PngdHeader(C.Structure):
+    """struct pf_pngd_header of include/pf_hip.h"""
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "depth", "color_type", "interlace", "channels", "bpp", "has_trns", "plte_entries",
+                                         "idat_chunks")] + \
+               [(n, C.c_int64) for n in ("rowbytes", "inflated_bytes", "compressed_bytes")] + [("palette", C.c_uint8 * 768)]
+
+
 # name -> argtypes (every function returns int status except pf_last_error / pf_version)
 SIGNATURES = {
     "pf_conv": [C.POINTER(ConvParams), vp],
@@ -158,6 +165,19 @@ SIGNATURES = {
     "pf_jpeg_prog_dc_refine": [C.POINTER(JpegHeader), C.POINTER(JpegProgScan), vp, cl, vp, vp, vp, vp],
     "pf_jpeg_prog_nonzero_mask": [C.POINTER(JpegHeader), C.POINTER(JpegProgScan), vp, vp, vp, vp],
     "pf_jpeg_prog_apply_refinement": [C.POINTER(JpegHeader), C.POINTER(JpegProgScan), vp, vp, vp, vp],
+    # PNG decoding of the input image (png_decode.hip); parse and the three *_host entry points are host-only
+    "pf_pngd_parse": [vp, cl, ci, C.POINTER(PngdHeader), vp, cl, C.POINTER(cl)],
+    "pf_pngd_find_host": [vp, cl, C.c_uint32, vp, cl, C.POINTER(cl)],
+    "pf_pngd_scan_host": [vp, cl, C.c_uint32, vp, ci, C.c_uint32, C.c_uint32, vp],
+    "pf_pngd_inflate_model_host": [vp, cl, cl, C.c_uint32, vp, vp],
+    "pf_pngd_find": [vp, cl, C.c_uint32, vp, C.c_uint32, vp, vp],
+    "pf_pngd_scan": [vp, cl, C.c_uint32, vp, ci, C.c_uint32, C.c_uint32, vp, vp],
+    "pf_pngd_inflate": [vp, cl, C.c_uint32, vp, ci, C.c_uint32, vp, vp, vp, vp],
+    "pf_pngd_resolve": [vp, vp, C.c_uint32, ci, vp, vp],
+    "pf_pngd_unfilter": [vp, C.POINTER(PngdHeader), vp, vp, vp],
+    "pf_pngd_expand": [vp, C.POINTER(PngdHeader), vp, vp, vp, vp],
+    "pf_pngd_adler": [vp, cl, vp, vp, vp],
+    "pf_pngd_to_rgb8": [vp, ci, ci, ci, ci, vp, vp],
 }
 NON_STATUS = ("pf_last_error", "pf_version", "pf_percentile_workspace_bytes", "pf_conv_winograd_fused_supported", "pf_gemm_split3_route",
               "pf_gemm_f16x2_points_route", "pf_gemm_f16x2_points_route_ex", "pf_conv_winograd_f16x2_supported_ex",

@@ -1384,5 +1384,78 @@ class HipOps:
         check(_L.pf_jpeg_prog_apply_refinement(C.byref(header), C.byref(scan), _p(records), _p(block_map), _p(coef), _stream()),
               "pf_jpeg_prog_apply_refinement")
 
+    # ---------------- PNG decoding of the input image (png_decode.hip); parse and chain walk live in preprocess ----------------
+    @staticmethod
+    def pngd_find(words, nbits, cand, count):
+        """words int32 (the deflate stream, zero padded by PF_PNGD_PAD_WORDS words) -> cand int32 [capacity] and count int32 [1] (keeps counting past
+        the capacity), all on the device"""
+        assert words.dtype == torch.int32 and cand.dtype == torch.int32 and count.dtype == torch.int32 and count.numel() == 1
+        assert words.is_contiguous() and cand.is_contiguous() and 0 < nbits <= 32 * (words.numel() - 2)
+        check(_L.pf_pngd_find(_p(words), words.numel(), int(nbits), _p(cand), cand.numel(), _p(count), _stream()), "pf_pngd_find")
+
+    @staticmethod
+    def pngd_scan(words, nbits, starts, n, max_block_bits, expected, records):
+        """starts int32 [>= n] -> records int32 [n,4] = {start bit, end bit, output bytes, status | BFINAL << 8}"""
+        assert words.dtype == torch.int32 and starts.dtype == torch.int32 and records.dtype == torch.int32
+        assert words.is_contiguous() and starts.is_contiguous() and records.is_contiguous() and 0 < nbits <= 32 * (words.numel() - 2)
+        assert 0 <= n <= starts.numel() and records.numel() >= 4 * n
+        check(_L.pf_pngd_scan(_p(words), words.numel(), int(nbits), _p(starts), int(n), int(max_block_bits), int(expected), _p(records), _stream()), "pf_pngd_scan")
+        return records
+
+    @staticmethod
+    def pngd_inflate(words, nbits, blocks, expected, lit, ref, status):
+        """blocks int32 [nblocks,4] = {start, type, output offset, output bytes} -> lit uint8 [expected], ref int32 [expected]"""
+        assert words.dtype == torch.int32 and blocks.dtype == torch.int32 and lit.dtype == torch.uint8 and ref.dtype == torch.int32
+        assert all(t.is_contiguous() for t in (words, blocks, lit, ref)) and 0 < nbits <= 32 * (words.numel() - 2)
+        assert blocks.dim() == 2 and blocks.shape[1] == 4 and lit.numel() == expected and ref.numel() == expected
+        assert status.dtype == torch.int32 and status.numel() >= 1
+        check(_L.pf_pngd_inflate(_p(words), words.numel(), int(nbits), _p(blocks), blocks.shape[0], int(expected), _p(lit), _p(ref), _p(status), _stream()),
+              "pf_pngd_inflate")
+
+    @staticmethod
+    def pngd_resolve(lit, ref, rounds, out):
+        """`rounds` pointer-jumping launches over ref (in place), then out[i] = lit[ref[i]]"""
+        assert lit.dtype == torch.uint8 and ref.dtype == torch.int32 and out.dtype == torch.uint8
+        assert lit.is_contiguous() and ref.is_contiguous() and out.is_contiguous() and lit.numel() == ref.numel() == out.numel()
+        check(_L.pf_pngd_resolve(_p(lit), _p(ref), ref.numel(), int(rounds), _p(out), _stream()), "pf_pngd_resolve")
+        return out
+
+    @staticmethod
+    def pngd_unfilter(header, inflated, recon, status):
+        """inflated uint8 [height * (1 + rowbytes)] -> recon uint8 [height * rowbytes]"""
+        assert inflated.dtype == torch.uint8 and inflated.is_contiguous() and inflated.numel() == header.inflated_bytes
+        assert recon.is_contiguous() and recon.numel() * recon.element_size() == header.height * header.rowbytes
+        assert status.dtype == torch.int32 and status.numel() >= 1
+        check(_L.pf_pngd_unfilter(_p(inflated), C.byref(header), _p(recon), _p(status), _stream()), "pf_pngd_unfilter")
+        return recon
+
+    @staticmethod
+    def pngd_expand(header, recon, palette, image, status):
+        """recon -> image for sub-byte samples, a palette (uint8 [768] on the device, else None) and 16-bit samples"""
+        assert recon.dtype == torch.uint8 and recon.is_contiguous() and recon.numel() == header.height * header.rowbytes
+        out_ch = 3 if header.color_type == 3 else header.channels
+        assert image.is_contiguous() and image.numel() == header.height * header.width * out_ch
+        assert image.element_size() == (2 if header.depth == 16 else 1)
+        assert palette is None or (palette.dtype == torch.uint8 and palette.numel() == 768 and palette.is_contiguous())
+        check(_L.pf_pngd_expand(_p(recon), C.byref(header), None if palette is None else _p(palette), _p(image), _p(status), _stream()),
+              "pf_pngd_expand")
+        return image
+
+    @staticmethod
+    def pngd_adler(data, sums, result):
+        """Adler-32 of data (uint8, device) -> result int32 [>= 1]; sums: int64 [2] of workspace"""
+        assert data.dtype == torch.uint8 and data.is_contiguous() and sums.dtype == torch.int64 and sums.numel() >= 2 and result.dtype == torch.int32
+        check(_L.pf_pngd_adler(_p(data), data.numel(), _p(sums), _p(result), _stream()), "pf_pngd_adler")
+
+    @staticmethod
+    def pngd_to_rgb8(image, rgb):
+        """a decoded PNG (uint8 or uint16; [H,W] or [H,W,C]) -> rgb uint8 [H,W,3]: grey replicated, alpha dropped, the high byte of 16 bits"""
+        H, W = image.shape[0], image.shape[1]
+        ch = 1 if image.dim() == 2 else image.shape[2]
+        assert image.is_contiguous() and image.element_size() in (1, 2) and rgb.dtype == torch.uint8 and rgb.is_contiguous()
+        assert tuple(rgb.shape) == (H, W, 3)
+        check(_L.pf_pngd_to_rgb8(_p(image), H, W, ch, 8 * image.element_size(), _p(rgb), _stream()), "pf_pngd_to_rgb8")
+        return rgb
+
 
 ops = HipOps()

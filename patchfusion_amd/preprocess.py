@@ -390,6 +390,354 @@ def _decode_jpeg_progressive(host, ops, dev, entropy, apply_orientation, S, cap)
     return rgb, info
 
 
+# ---------------------------------------------------------------- PNG
+# Defaults of decode_png.  A zlib block holds at most 32 767 symbols of at most 48 bits (15 + 5 + 15 + 13) behind about 4.5 kbit of
+# header: under 1.6 Mbit, so 2^21 bits bound every block zlib writes.  zlib chooses a fixed block only where it is smaller than a dynamic
+# one (typically the last), and each one the walk meets costs one more scan pass: 8 passes.
+# The inflate arm was chosen by tools/png_decode_time.py (profiles/png_decode_time.json, one MI355X).  The device arm decodes a block
+# sequentially on one wave, twice (scan and inflate passes), so those two passes take about 14 ms (PIL level 6) to 27 ms (level 1)
+# whatever the file's size: at 3840x2160 that beats the host arm (RGB8 level 6: 32.6 ms against 76.2 ms, and 93.4 ms for PIL + upload),
+# at 2048x1024 it does not (18.8 ms against 16.9 ms; level 1: 32.1 against 22.4).  The rule was "default only if faster at both sizes",
+# so 'host' is the default and 'device' is opt-in.
+PNG_MAX_BLOCK_BITS = 1 << 21
+PNG_MAX_CHAIN_ROUNDS = 8
+PNG_INFLATE = "host"
+PNG_S_OK, PNG_S_INVALID, PNG_S_LIMIT, PNG_S_EOS, PNG_S_SIZE, PNG_S_DIST = range(6)       # PF_PNGD_S_* of pf_hip.h
+PNG_F_STREAM, PNG_F_DISTANCE, PNG_F_FILTER, PNG_F_PLTE = 1, 2, 4, 8                    # PF_PNGD_F_*
+PNG_PAD_WORDS = 2                                                                      # PF_PNGD_PAD_WORDS
+
+
+class PngError(ValueError):
+    """a PNG file decode_png refuses or cannot decode; .code is the PF_PNGD_E_* status of include/pf_hip.h"""
+
+    def __init__(self, code, what):
+        super().__init__(f"png: {what}")
+        self.code = code
+
+
+def _png_refusal(name, what):
+    return type(name, (PngError,), {"__doc__": what})
+
+
+PNG_ERRORS = {
+    80: _png_refusal("PngSignature", "not a PNG file (bad signature)"),
+    81: _png_refusal("PngChunk", "a chunk's length runs past the file, a critical chunk is unknown, or tRNS does not fit the colour type"),
+    82: _png_refusal("PngOrder", "chunks out of order (IHDR first, PLTE before IDAT, IDAT consecutive, IEND last)"),
+    83: _png_refusal("PngCrc", "CRC mismatch in a critical chunk"),
+    84: _png_refusal("PngIhdr", "IHDR holds a combination the specification forbids"),
+    85: _png_refusal("PngInterlaced", "Adam7 interlaced files are not supported"),
+    86: _png_refusal("PngZlibHeader", "zlib header: method other than deflate, window above 32 KiB, preset dictionary, or bad check bits"),
+    87: _png_refusal("PngStream", "the deflate stream is invalid or truncated"),
+    88: _png_refusal("PngDistance", "a match reaches before the start of the output"),
+    89: _png_refusal("PngSize", "the inflated size is not height * (1 + row bytes)"),
+    90: _png_refusal("PngAdler", "Adler-32 mismatch"),
+    91: _png_refusal("PngFilter", "a row's filter type is above 4"),
+    92: _png_refusal("PngPalette", "PLTE is missing or invalid, or a pixel indexes past it"),
+    93: _png_refusal("PngIdatCrc", "CRC mismatch in an IDAT chunk"),
+}
+PngInterlaced = PNG_ERRORS[85]
+
+
+def _png_raise(code):
+    cls = PNG_ERRORS[code]
+    raise cls(code, cls.__doc__)
+
+
+def _png_check(rc, step):
+    if rc == 0:
+        return
+    if rc in PNG_ERRORS:
+        _png_raise(rc)
+    raise PngError(rc, f"{step} failed (status {rc})")
+
+
+class PngInfo:
+    """what decode_png reports next to the image"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return "PngInfo(" + ", ".join(f"{k}={v!r}" for k, v in self.__dict__.items()) + ")"
+
+
+class PngHost:
+    """the HOST ONLY steps of the PNG decoder (csrc/png_host.h through the C ABI, and the chain walk): no GPU call"""
+
+    def __init__(self, data, check_idat_crc=False):
+        self.lib = _lib.load()
+        self.data = np.frombuffer(bytes(data), dtype=np.uint8)
+        self.header = _lib.PngdHeader()
+        buf = np.zeros(self.data.size + 16, dtype=np.uint8)
+        n = C.c_long()
+        _png_check(self.lib.pf_pngd_parse(self.data.ctypes.data, self.data.size, int(bool(check_idat_crc)), C.byref(self.header), buf.ctypes.data,
+                                          self.data.size, C.byref(n)), "pf_pngd_parse")
+        self.deflate = buf[:n.value]                 # raw deflate data and the Adler-32 behind it (the zlib header is checked and gone)
+
+    def words(self):
+        """the deflate bytes as the device wants them: little-endian words with PNG_PAD_WORDS zero words behind"""
+        n = self.deflate.size
+        w = np.zeros(4 * ((n + 3) // 4 + PNG_PAD_WORDS), dtype=np.uint8)
+        w[:n] = self.deflate
+        return w.view(np.int32)
+
+    def bits(self, p, k):
+        """k <= 16 bits at bit p of the deflate data, first bit lowest (zeros past the end)"""
+        d, i = self.deflate, p >> 3
+        v = sum(int(d[i + j]) << (8 * j) for j in range(3) if i + j < d.size)
+        return (v >> (p & 7)) & ((1 << k) - 1)
+
+    def inflate(self):
+        """stdlib zlib over the raw deflate data -> (the inflated bytes, the Adler-32 the file states)"""
+        import zlib
+        expected = self.header.inflated_bytes
+        z = zlib.decompressobj(wbits=-15)
+        try:
+            out = z.decompress(self.deflate.tobytes(), expected + 1)
+        except zlib.error as e:
+            _png_raise(88 if "distance too far back" in str(e) else 87)
+        if len(out) > expected or (z.eof and len(out) != expected):
+            _png_raise(89)
+        if not z.eof or len(z.unused_data) < 4:
+            _png_raise(87)
+        return np.frombuffer(bytearray(out), dtype=np.uint8), int.from_bytes(z.unused_data[:4], "big")
+
+
+class PngChain:
+    """The chain walk over the scan records: from bit 0, a scanned block jumps to its recorded end, a stored block is closed-form from the
+    host's bytes.  step() -> None when the final block was reached (blocks, adler and counts are set), or the start bit of a fixed block
+    that has no record yet (add() its record and call step() again).  A stream that cannot be right raises; .giveup names what only the
+    host arm can complete."""
+
+    def __init__(self, host):
+        self.host, self.table, self.blocks, self.p, self.total, self.giveup = host, {}, [], 0, 0, None
+        self.counts = {"dynamic": 0, "fixed": 0, "stored": 0}
+
+    def add(self, records):
+        for start, end, out, st in np.asarray(records, dtype=np.int64).reshape(-1, 4):
+            self.table[int(start) & 0xffffffff] = (int(end) & 0xffffffff, int(out) & 0xffffffff, int(st) & 255)
+
+    def step(self):
+        host = self.host
+        d, nbits, expected = host.deflate, 8 * host.deflate.size, host.header.inflated_bytes
+        while True:
+            p = self.p
+            if p + 3 > nbits:
+                _png_raise(87)
+            head = host.bits(p, 3)
+            kind = head >> 1
+            if kind == 3:
+                _png_raise(87)
+            if kind == 0:
+                at = (p + 3 + 7) // 8
+                if at + 4 > d.size:
+                    _png_raise(87)
+                n, inv = int(d[at]) | int(d[at + 1]) << 8, int(d[at + 2]) | int(d[at + 3]) << 8
+                if n ^ inv != 0xffff or at + 4 + n > d.size:
+                    _png_raise(87)
+                self.blocks.append((at + 4, 0, self.total, n))
+                self.p, out = 8 * (at + 4 + n), n
+            else:
+                rec = self.table.get(p)
+                if rec is None:
+                    if kind == 1:
+                        return p
+                    _png_raise(87)                   # a dynamic header the finder's test refuses is not a header
+                end, out, st = rec
+                if st == PNG_S_LIMIT:
+                    self.giveup = "a block is longer than max_block_bits"
+                    return None
+                if st != PNG_S_OK:
+                    _png_raise(89 if st == PNG_S_SIZE else 87)
+                self.blocks.append((p, kind, self.total, out))
+                self.p = end
+            self.counts[("stored", "fixed", "dynamic")[kind]] += 1
+            self.total += out
+            if self.total > expected:
+                _png_raise(89)
+            if head & 1:
+                break
+        if self.total != expected:
+            _png_raise(89)
+        at = (self.p + 7) // 8
+        if at + 4 > d.size:
+            _png_raise(87)
+        self.adler = int.from_bytes(d[at:at + 4].tobytes(), "big")
+        return None
+
+
+def png_inflate_device(host, ops, dev, max_chain_rounds, max_block_bits, timing=None):
+    """the device inflate of decode_png on a PngHost -> (inflated uint8 [height * (1 + rowbytes)] on the device or None, stats).  None:
+    stats['fallback_reason'] says what only the host arm can complete; nothing was decoded.  The stream's own errors raise.
+    timing: a dict that receives the seconds of 'finder', 'scan', 'chain_walk' (with its copies), 'inflate' and 'resolve'; each part then
+    ends in a synchronise, which the untimed path does not do."""
+    import time
+    h = host.header
+    n, expected = host.deflate.size, h.inflated_bytes
+    stats = dict(candidates=0, chain_rounds=0, resolve_rounds=0, blocks=None, bytes_uploaded=0, bytes_downloaded=0, fallback_reason=None, adler=None)
+    t0 = time.perf_counter()
+
+    def tick(key):
+        nonlocal t0
+        if timing is not None:
+            if dev.type == "cuda":
+                torch.cuda.synchronize(dev)
+            now = time.perf_counter()
+            timing[key] = timing.get(key, 0.0) + now - t0
+            t0 = now
+
+    def give_up(why):
+        stats["fallback_reason"] = why
+        return None, stats
+
+    if n == 0:
+        _png_raise(87)
+    if n >= (1 << 28) or expected >= (1 << 31):
+        return give_up("the stream is too large for 32-bit positions")
+    if max_chain_rounds < 1:
+        return give_up("max_chain_rounds allows no scan pass")
+    nbits = 8 * n
+    w = host.words()
+    words = torch.from_numpy(w).to(dev)
+    stats["bytes_uploaded"] += w.nbytes
+    cand = torch.empty(n // 16 + 64, dtype=torch.int32, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    ops.pngd_find(words, nbits, cand, count)
+    ncand = int(count.cpu()[0])
+    stats["bytes_downloaded"] += 4
+    stats["candidates"] = ncand
+    tick("finder")
+    if ncand > cand.numel():
+        return give_up("the candidate list overflowed")
+    chain = PngChain(host)
+    starts, nstart = cand, ncand
+    while True:
+        stats["chain_rounds"] += 1
+        if nstart:
+            records = torch.empty((nstart, 4), dtype=torch.int32, device=dev)
+            ops.pngd_scan(words, nbits, starts, nstart, max_block_bits, min(expected, 0xffffffff), records)
+            tick("scan")
+            chain.add(records.cpu().numpy())
+            stats["bytes_downloaded"] += 16 * nstart
+        need = chain.step()
+        if need is None:
+            break
+        if stats["chain_rounds"] >= max_chain_rounds:
+            tick("chain_walk")
+            return give_up("more fixed blocks than max_chain_rounds scan passes reach")
+        starts, nstart = torch.tensor([need], dtype=torch.int64).to(torch.int32).to(dev), 1
+        stats["bytes_uploaded"] += 4
+        tick("chain_walk")
+    if chain.giveup:
+        tick("chain_walk")
+        return give_up(chain.giveup)
+    table = np.asarray(chain.blocks, dtype=np.int64).astype(np.uint32).view(np.int32).reshape(-1, 4)
+    blocks = torch.from_numpy(table).to(dev)
+    stats["bytes_uploaded"] += table.nbytes
+    tick("chain_walk")
+    stats["blocks"], stats["adler"] = dict(chain.counts), chain.adler
+    lit = torch.empty(expected, dtype=torch.uint8, device=dev)
+    ref = torch.empty(expected, dtype=torch.int32, device=dev)
+    stats["status"] = torch.zeros(1, dtype=torch.int32, device=dev)
+    ops.pngd_inflate(words, nbits, blocks, expected, lit, ref, stats["status"])
+    tick("inflate")
+    stats["resolve_rounds"] = max(len(chain.blocks) - 1, 0).bit_length() + 1          # ceil(log2(blocks)) + 1
+    inflated = ops.pngd_resolve(lit, ref, stats["resolve_rounds"], torch.empty(expected, dtype=torch.uint8, device=dev))
+    tick("resolve")
+    return inflated, stats
+
+
+def decode_png(data, device="cuda", inflate=None, verify=True, max_chain_rounds=None, max_block_bits=None, ops=None, timing=None):
+    """PNG (bytes or a path) -> (device tensor, PngInfo), lossless and bit-exact with the PNG specification: uint8 or torch.uint16 (native
+    byte order), [H,W] for grey, [H,W,2] grey+alpha, [H,W,3] RGB, [H,W,4] RGBA.  A palette expands to uint8 [H,W,3] (tRNS is ignored and
+    reported as info.has_trns); grey of 1 / 2 / 4 bits expands to uint8 by bit replication (x255, x85, x17) as libpng's
+    expand_gray_1_2_4_to_8, PIL and cv2 do.  Every non-interlaced colour type and bit depth is accepted; ancillary chunks are skipped.
+    inflate='device' uploads the compressed stream and inflates it block-parallel on the GPU; 'host' runs the standard library's zlib and
+    uploads the filtered bytes; unfilter, expansion and the Adler-32 are the same device code either way, and so are the pixels.  When the
+    device arm gives up (candidate list overflow, a block above max_block_bits, more fixed blocks than max_chain_rounds scan passes) the
+    host arm completes the file: info.inflate and info.fallback_reason say so.  verify=True checks the Adler-32 (computed on the device),
+    verify='full' also the CRC-32 of the IDAT chunks (on the host: one more pass over the compressed bytes), verify=False neither.
+    Unsupported or broken files raise a PngError subclass (a ValueError); there is no fallback to a host image library."""
+    inflate = PNG_INFLATE if inflate is None else inflate
+    if inflate not in ("device", "host"):
+        raise ValueError(f"inflate must be 'device' or 'host', got {inflate!r}")
+    if verify not in (True, False, "full"):
+        raise ValueError(f"verify must be True, False or 'full', got {verify!r}")
+    rounds_cap = PNG_MAX_CHAIN_ROUNDS if max_chain_rounds is None else int(max_chain_rounds)
+    bits_cap = PNG_MAX_BLOCK_BITS if max_block_bits is None else int(max_block_bits)
+    if rounds_cap < 0:
+        raise ValueError("max_chain_rounds must be >= 0")
+    if bits_cap < 64 or bits_cap > (1 << 31):
+        raise ValueError(f"max_block_bits must be in 64 .. 2^31, got {max_block_bits}")
+    if isinstance(data, (str, os.PathLike)):
+        with open(data, "rb") as f:
+            data = f.read()
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise ValueError(f"decode_png expects bytes or a path, got {type(data).__name__}")
+    if ops is None:
+        from .hip_ops import ops as _ops        # fails loudly when the HIP extension is missing
+        ops = _ops
+    import time
+    dev = torch.device(device)
+    host = PngHost(data, check_idat_crc=verify == "full")
+    h = host.header
+    expected = h.inflated_bytes
+    if expected >= (1 << 31):
+        raise PngError(89, "images above 2 GiB of filtered bytes are not supported")
+    used, inflated, stated = inflate, None, None
+    stats = dict(candidates=0, chain_rounds=0, resolve_rounds=0, blocks=None, bytes_uploaded=0, bytes_downloaded=0, fallback_reason=None)
+    if inflate == "device":
+        inflated, stats = png_inflate_device(host, ops, dev, rounds_cap, bits_cap, timing)
+        stated = stats.get("adler")
+        if inflated is None:
+            used = "host"
+    if used == "host":
+        t0 = time.perf_counter()
+        raw, stated = host.inflate()
+        inflated = torch.from_numpy(raw).to(dev)
+        stats["bytes_uploaded"] += raw.nbytes
+        if timing is not None:
+            timing["host_inflate"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    result = torch.zeros(2, dtype=torch.int32, device=dev)             # {Adler-32, status flags}: the one 8-byte copy back
+    status = result[1:]
+    if "status" in stats:
+        status.copy_(stats.pop("status"))
+    if verify:
+        ops.pngd_adler(inflated, torch.empty(2, dtype=torch.int64, device=dev), result)
+        if timing is not None and dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+            timing["adler"] = time.perf_counter() - t0
+            t0 = time.perf_counter()
+    H, W, ch = h.height, h.width, 3 if h.color_type == 3 else h.channels
+    shape = (H, W) if ch == 1 else (H, W, ch)
+    image = torch.empty(shape, dtype=torch.uint16 if h.depth == 16 else torch.uint8, device=dev)
+    if h.depth == 8 and h.color_type != 3:
+        ops.pngd_unfilter(h, inflated, image, status)                   # the unfiltered rows are the image
+    else:
+        recon = ops.pngd_unfilter(h, inflated, torch.empty(H * h.rowbytes, dtype=torch.uint8, device=dev), status)
+        palette = None
+        if h.color_type == 3:
+            palette = torch.from_numpy(np.frombuffer(bytes(h.palette), dtype=np.uint8).copy()).to(dev)
+            stats["bytes_uploaded"] += 768
+        ops.pngd_expand(h, recon, palette, image, status)
+    got = result.cpu().numpy().view(np.uint32)
+    stats["bytes_downloaded"] += 8
+    if timing is not None:
+        timing["unfilter_expand"] = time.perf_counter() - t0
+    flags = int(got[1])
+    for bit, code in ((PNG_F_DISTANCE, 88), (PNG_F_STREAM, 87), (PNG_F_FILTER, 91), (PNG_F_PLTE, 92)):
+        if flags & bit:
+            _png_raise(code)
+    if verify and int(got[0]) != stated:
+        _png_raise(90)
+    info = PngInfo(width=W, height=H, bit_depth=h.depth, color_type=h.color_type, channels=h.channels, has_trns=bool(h.has_trns),
+                   inflate=used, fallback_reason=stats["fallback_reason"], blocks=stats["blocks"], candidates=stats["candidates"],
+                   chain_rounds=stats["chain_rounds"], resolve_rounds=stats["resolve_rounds"], compressed_bytes=int(h.compressed_bytes),
+                   bytes_uploaded=stats["bytes_uploaded"], bytes_downloaded=stats["bytes_downloaded"])
+    return image, info
+
+
 class ImagePreprocessor:
     def __init__(self, image_resolution=(2160, 3840), process_shape=(392, 518), dataset_name="general", device="cuda", ops=None):
         if ops is None:
@@ -418,12 +766,22 @@ class ImagePreprocessor:
             self.ops.resize_bilinear_f32(image_hr[c], image_lr[c])
         return {"image_hr": image_hr, "image_lr": image_lr}
 
-    def read(self, path_or_bytes, **kw):
-        """decode_jpeg followed by __call__: the file never becomes a host array.  The EXIF orientation is applied for the datasets the
-        reference reads with cv2.imread ('mid', general) and not for 'cityscapes', which it reads with PIL (no rotation).  'u4k' files are
-        raw arrays, not JPEG: refused."""
+    def read(self, path_or_bytes, png_options=None, **kw):
+        """decode_jpeg or decode_png (by the file's signature) followed by __call__: the file never becomes a host array.
+        JPEG: the EXIF orientation is applied for the datasets the reference reads with cv2.imread ('mid', general) and not for
+        'cityscapes', which it reads with PIL (no rotation); kw goes to decode_jpeg.  PNG: decode_png(**png_options), then one kernel to
+        uint8 [H,W,3]: grey replicated, alpha dropped, 16-bit samples keep their high byte (libpng's strip_16, what cv2.imread and, for
+        16-bit RGB, PIL do); kw (JPEG-only keywords) is ignored.  'u4k' files are raw arrays, not JPEG: refused."""
         if self.dataset_name == "u4k":
             raise ValueError("dataset 'u4k' stores raw arrays, not JPEG files: there is nothing to decode")
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as f:
+                path_or_bytes = f.read()
+        if isinstance(path_or_bytes, (bytes, bytearray, memoryview)) and bytes(path_or_bytes[:8]) == b"\x89PNG\r\n\x1a\n":
+            image, self.last_png_info = decode_png(path_or_bytes, device=self.device, ops=self.ops, **(png_options or {}))
+            if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3:
+                image = self.ops.pngd_to_rgb8(image, torch.empty(tuple(image.shape[:2]) + (3,), dtype=torch.uint8, device=self.device))
+            return self(image)
         kw.setdefault("apply_orientation", self.dataset_name != "cityscapes")
         rgb, self.last_jpeg_info = decode_jpeg(path_or_bytes, device=self.device, ops=self.ops, **kw)
         return self(rgb)
