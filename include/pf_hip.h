@@ -67,6 +67,15 @@ int pf_conv(const pf_conv_params* p, void* stream);
 /* timing helper for the roofline entry of bench.py: runs `iters` launches bracketed by HIP events on
  * `stream`, returns the average milliseconds per launch in *ms */
 int pf_conv_timed(const pf_conv_params* p, int iters, float* ms, void* stream);
+/* Introspection for the tests: the kernel variant that the calling thread's last pf_conv launched (0 before the first launch).  Read-only; no
+ * dispatch rule reads it and nothing is launched.  code = family * 10^8 + shape * 100 + shuffle * 10 + relu_in, shuffle = 0 | 2 | 4 ..., with
+ *   family 1: conv3x3_halo_kernel<WN, FM, FN>        shape = WN * 100 + FM * 10 + FN      (121, 122, 242, 243)
+ *   family 2: gemm_persist_kernel<BM, BN>             shape = BM * 1000 + BN               (128128, 128096, 128064, 144128, 144064, 256128)
+ *   family 3: conv_igemm_big_kernel (256 x 128)       shape = 256128
+ *   family 4: conv_igemm_kernel<bf16, BM, BN>         shape = BM * 1000 + BN               (128128, 128096, 128064, 256032, 256016)
+ *   family 5: conv_igemm_kernel<float, BM, BN>        shape = BM * 1000 + BN               (the above, 64064, 256256); a layer split into a body
+ *             and a remainder launch reports the remainder's tile */
+int pf_conv_last_variant(void);
 
 /* Winograd F(m x m, 3 x 3), m = 2 or 4, for float32 3x3 / stride 1 / pad 1 layers (same reference layers as pf_conv): `p` describes
  * the convolution exactly as for pf_conv (x, bias, res, res2, y, act NONE | RELU, relu_in; p->w is not read; scale must be NULL,

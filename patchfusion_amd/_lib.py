@@ -181,7 +181,8 @@ SIGNATURES = {
 }
 NON_STATUS = ("pf_last_error", "pf_version", "pf_percentile_workspace_bytes", "pf_conv_winograd_fused_supported", "pf_gemm_split3_route",
               "pf_gemm_f16x2_points_route", "pf_gemm_f16x2_points_route_ex", "pf_conv_winograd_f16x2_supported_ex",
-              "pf_wino_f16x2_scratch_bytes", "pf_conv_winograd_f16x2_supported", "pf_vit_attention_rpb_bf16_lds_bytes")   # entry points that do not return a status
+              "pf_wino_f16x2_scratch_bytes", "pf_conv_winograd_f16x2_supported", "pf_vit_attention_rpb_bf16_lds_bytes",
+              "pf_conv_last_variant")   # entry points that do not return a status
 
 _lib = None
 
@@ -222,6 +223,8 @@ def load():
     lib.pf_conv_winograd_f16x2_supported.argtypes = [C.POINTER(ConvParams), ci, ci, C.c_long]
     lib.pf_vit_attention_rpb_bf16_lds_bytes.restype = ci              # bytes (or -1), not a status
     lib.pf_vit_attention_rpb_bf16_lds_bytes.argtypes = [ci, ci, ci]
+    lib.pf_conv_last_variant.restype = ci                             # variant code of the thread's last pf_conv launch, not a status
+    lib.pf_conv_last_variant.argtypes = []
     _lib = lib
     return lib
 

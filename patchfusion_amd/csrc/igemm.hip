@@ -588,6 +588,13 @@ inline int launch_status() {
   return g_launch_status == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
 }
 
+// the kernel variant the last pf_conv of this thread launched (pf_conv_last_variant; codes in include/pf_hip.h): written by the four launchers,
+// read by the tests only -- no dispatch rule looks at it
+thread_local int g_last_variant = 0;
+inline void note_variant(int family, int shape, int shuffle, bool relu_in) {
+  g_last_variant = family * 100000000 + shape * 100 + (shuffle > 1 ? shuffle : 0) * 10 + (relu_in ? 1 : 0);
+}
+
 // candidate shapes of the persistent GEMM: {BM, BN, WM, WN}; resident blocks per CU follow from the 160 KiB of LDS
 template <int BM, int BN, int WM, int WN>
 struct PersistCfg {
@@ -606,6 +613,7 @@ int launch_persist(const pf_conv_params& p, hipStream_t st) {
   const long M = (long)p.B * p.OH * p.OW;
   const long tiles = ((M + BM - 1) / BM) * ((p.Cout + BN - 1) / BN);
   const long slots = 256L * C::occ;                      // resident blocks
+  note_variant(2, BM * 1000 + BN, 0, RELU_IN);
   hipLaunchKernelGGL(kern, dim3((unsigned)(tiles < slots ? tiles : slots)), dim3(64 * WM * WN), smem, st, p);
   return launch_status();
 }
@@ -831,6 +839,7 @@ int launch_big(const pf_conv_params& p, hipStream_t st) {
   ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, attr_done);
   const long M = (long)p.B * p.OH * p.OW;
   const long mt = (M + 255) / 256, nt = (p.Cout + 127) / 128;
+  note_variant(3, 256128, p.shuffle, RELU_IN);
   hipLaunchKernelGGL(kern, dim3((unsigned)(mt * nt)), dim3(512), smem, st, p);
   return launch_status();
 }
@@ -1247,6 +1256,7 @@ int launch_halo(const pf_conv_params& p, hipStream_t st) {
   ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, attr_done);
   const long tiles = (long)p.B * ((p.H + 15) / 16) * ((p.W + 31) / 32);
   const long nt = (p.Cout + BN - 1) / BN;
+  note_variant(1, WN * 100 + FM * 10 + FN, 0, RELU_IN);
   hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * nt)), dim3(512), smem, st, p);
   return launch_status();
 }
@@ -1262,6 +1272,7 @@ int launch_cfg2(const pf_conv_params& p, hipStream_t st) {
   ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, attr_done);
   const long M = (long)p.B * p.OH * p.OW;
   const long mt = (M + BM - 1) / BM, nt = (p.Cout + BN - 1) / BN;
+  note_variant(sizeof(T) == 2 ? 4 : 5, BM * 1000 + BN, p.shuffle, RELU_IN);
   hipLaunchKernelGGL(kern, dim3((unsigned)(mt * nt), (unsigned)(p.batch > 1 ? p.batch : 1)), dim3(64 * WM * WN), smem, st, p);
   return launch_status();
 }
@@ -1486,6 +1497,7 @@ int validate(const pf_conv_params* p) {
 
 extern "C" const char* pf_last_error(void) { return g_err; }
 extern "C" int pf_version(void) { return 1; }
+extern "C" int pf_conv_last_variant(void) { return g_last_variant; }
 
 extern "C" int pf_conv(const pf_conv_params* p, void* stream) {
   if (!p) return PF_ERR_ARG;

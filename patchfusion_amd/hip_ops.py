@@ -264,6 +264,12 @@ def wino3_window(B, H, W, pw):
     return window, nwin, (36 * window * pw.cin * 3 + 1) // 2, 36 * window * pw.cout
 
 
+def last_conv_variant():
+    """code of the kernel variant the calling thread's last pf_conv launched (include/pf_hip.h pf_conv_last_variant: family, tile shape, shuffle,
+    RELU_IN); 0 before the first launch.  For the tests (tests/test_bf16_grade_gpu.py): nothing on the product path reads it."""
+    return int(_L.pf_conv_last_variant())
+
+
 def _align16(*ts):
     """the 16-byte alignment of each tensor's data pointer: part of the plan key, because the route may depend on it (conv1x1_split3_layout_ok)"""
     return tuple(None if t is None else t.data_ptr() % 16 for t in ts)

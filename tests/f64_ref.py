@@ -1,5 +1,6 @@
 """Sampled float64 reference of the NHWC convolutions / linears and the element-wise error metric of the float32-grade checks
-(tests/test_float32_grade_gpu.py; CPU checks of the reference itself in tests/test_f64_ref_cpu.py).  No GPU needed.
+(tests/test_float32_grade_gpu.py; CPU checks of the reference itself in tests/test_f64_ref_cpu.py) and of the bf16-grade checks
+(tests/test_bf16_grade_gpu.py: bf16_excess / bf16_grade, proved on the CPU in tests/test_bf16_grade_ref_cpu.py).  No GPU needed.
 
 The reference evaluates the layer in float64 on the CPU at a chosen set of output pixels (rows of a linear), every output channel, in the epilogue
 order of tests/fake_ops.py: bias -> act -> scale -> res -> res2.  Next to it comes the magnitude of every element,
@@ -122,6 +123,36 @@ def float32_grade(e, base, norm_cap, elem_cap):
     """the bar of the float32-grade checks: e = (element-wise, normwise) of the route, base = the same of the float32 baseline on the same operands.
     Each at most twice the baseline's, normwise <= norm_cap, element-wise <= elem_cap."""
     return e[0] <= 2 * base[0] and e[1] <= 2 * base[1] and e[1] <= norm_cap and e[0] <= elem_cap
+
+
+def bf16_excess(y, ref, mag):
+    """what a stored output y [P, N] is off by beyond its own storage rounding, as (element-wise, normwise) like errors().  A bfloat16 y is a float32
+    value v rounded once to nearest, and a v that rounds to y lies within half a bfloat16 ulp of y (f64_image_ref.bf16_half_ulp, evaluated at the
+    STORED value), so
+
+        excess = max(0, |y - ref| - half_ulp_bf16(y)) / mag
+
+    is a lower bound of |v - ref| / mag: ~1e-8 for a float32-accumulated product rounded once, >= 3e-4 for a second rounding before a residual
+    add, for truncation, for a dropped K chunk (tests/test_bf16_grade_ref_cpu.py).  A float32 y (out_f32) has no storage rounding: errors()."""
+    if y.dtype != torch.bfloat16:
+        return errors(y, ref, mag)
+    from tests.f64_image_ref import bf16_half_ulp
+    y = y.detach().cpu().double()
+    if not torch.isfinite(y).all():
+        return float("inf"), float("inf")
+    d = ((y - ref).abs() - bf16_half_ulp(y)).clamp_min(0)
+    return float((d / (mag + TINY)).max()), float(d.max() / max(float(ref.abs().max()), TINY))
+
+
+BASE_FLOOR = 4 * 2.0 ** -24      # floor of a baseline's error (f64_image_ref.baseline_bar: one stray rounding in the baseline must not decide)
+
+
+def bf16_grade(e, base, elem_cap=None):
+    """the bar of the bf16-grade checks (tests/test_bf16_grade_gpu.py), after float32_grade: e = bf16_excess of the bf16 kernel, base = errors() of the
+    float32-MFMA kernel on the same bf16-valued operands.  The largest element-wise excess at most ELEM_CAP_GEMM and at most twice the baseline's
+    element-wise error, the baseline floored at 4 * 2^-24.  (No cap comes from the bf16 kernels' own measured error.)"""
+    cap = ELEM_CAP_GEMM if elem_cap is None else elem_cap
+    return e[0] <= cap and e[0] <= 2 * max(base[0], BASE_FLOOR)
 
 
 def old_normwise_bar(y, ref, tol=2e-4):
