@@ -715,6 +715,23 @@ int pf_pngd_unfilter(const uint8_t* inflated, const pf_pngd_header* header, uint
 int pf_pngd_expand(const uint8_t* recon, const pf_pngd_header* header, const uint8_t* palette, void* image, uint32_t* status, void* stream);
 int pf_pngd_adler(const uint8_t* data, long n, uint64_t* sums, uint32_t* result, void* stream);
 int pf_pngd_to_rgb8(const void* image, int height, int width, int channels, int bits, uint8_t* rgb, void* stream);
+/* Steps 3 and 5 with the symbols of a block decoded in parallel subsequences (csrc/png_inflate_par.hip; the scheme is stated in
+ * csrc/png_inflate.h): one workgroup of pf_pngd_par_window() threads per candidate / per block, every thread one lane of
+ * `subsequence_bits` bits (a multiple of 32 in 64 .. 65536).  The arguments and their checks are those of pf_pngd_scan / pf_pngd_inflate;
+ * the records are the same wherever pf_pngd_scan's status is PF_PNGD_S_OK and carry some other status elsewhere; after
+ * pf_pngd_inflate_par a reference points to a literal or into a strictly earlier lane's range, so pf_pngd_resolve needs
+ * ceil(log2(lane ranges + stored blocks)) + 1 rounds.  `max_rounds` (a device word, zeroed by the caller) is raised to the largest number
+ * of rounds a window needed.  The *_host entries run the same lane decoder through the same round schedule in plain loops on host
+ * pointers (no GPU call), for tests. */
+int pf_pngd_par_window(void);
+int pf_pngd_scan_par_host(const uint32_t* words, long nwords, uint32_t nbits, const uint32_t* starts, int n, uint32_t max_block_bits, uint32_t expected,
+                          uint32_t subsequence_bits, uint32_t* records, uint32_t* max_rounds);
+int pf_pngd_inflate_par_host(const uint32_t* words, long nwords, uint32_t nbits, const uint32_t* blocks, int nblocks, uint32_t expected,
+                             uint32_t subsequence_bits, uint8_t* lit, uint32_t* ref, uint32_t* status, uint32_t* max_rounds);
+int pf_pngd_scan_par(const uint32_t* words, long nwords, uint32_t nbits, const uint32_t* starts, int n, uint32_t max_block_bits, uint32_t expected,
+                     uint32_t subsequence_bits, uint32_t* records, uint32_t* max_rounds, void* stream);
+int pf_pngd_inflate_par(const uint32_t* words, long nwords, uint32_t nbits, const uint32_t* blocks, int nblocks, uint32_t expected,
+                        uint32_t subsequence_bits, uint8_t* lit, uint32_t* ref, uint32_t* status, uint32_t* max_rounds, void* stream);
 
 #ifdef __cplusplus
 }

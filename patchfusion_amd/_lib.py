@@ -165,7 +165,7 @@ SIGNATURES = {
     "pf_jpeg_prog_dc_refine": [C.POINTER(JpegHeader), C.POINTER(JpegProgScan), vp, cl, vp, vp, vp, vp],
     "pf_jpeg_prog_nonzero_mask": [C.POINTER(JpegHeader), C.POINTER(JpegProgScan), vp, vp, vp, vp],
     "pf_jpeg_prog_apply_refinement": [C.POINTER(JpegHeader), C.POINTER(JpegProgScan), vp, vp, vp, vp],
-    # PNG decoding of the input image (png_decode.hip); parse and the three *_host entry points are host-only
+    # PNG decoding of the input image (png_decode.hip); parse and the *_host entry points are host-only
     "pf_pngd_parse": [vp, cl, ci, C.POINTER(PngdHeader), vp, cl, C.POINTER(cl)],
     "pf_pngd_find_host": [vp, cl, C.c_uint32, vp, cl, C.POINTER(cl)],
     "pf_pngd_scan_host": [vp, cl, C.c_uint32, vp, ci, C.c_uint32, C.c_uint32, vp],
@@ -178,11 +178,15 @@ SIGNATURES = {
     "pf_pngd_expand": [vp, C.POINTER(PngdHeader), vp, vp, vp, vp],
     "pf_pngd_adler": [vp, cl, vp, vp, vp],
     "pf_pngd_to_rgb8": [vp, ci, ci, ci, ci, vp, vp],
+    "pf_pngd_scan_par_host": [vp, cl, C.c_uint32, vp, ci, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp],
+    "pf_pngd_inflate_par_host": [vp, cl, C.c_uint32, vp, ci, C.c_uint32, C.c_uint32, vp, vp, vp, vp],
+    "pf_pngd_scan_par": [vp, cl, C.c_uint32, vp, ci, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp],
+    "pf_pngd_inflate_par": [vp, cl, C.c_uint32, vp, ci, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp],
 }
 NON_STATUS = ("pf_last_error", "pf_version", "pf_percentile_workspace_bytes", "pf_conv_winograd_fused_supported", "pf_gemm_split3_route",
               "pf_gemm_f16x2_points_route", "pf_gemm_f16x2_points_route_ex", "pf_conv_winograd_f16x2_supported_ex",
               "pf_wino_f16x2_scratch_bytes", "pf_conv_winograd_f16x2_supported", "pf_vit_attention_rpb_bf16_lds_bytes",
-              "pf_conv_last_variant")   # entry points that do not return a status
+              "pf_conv_last_variant", "pf_pngd_par_window")   # entry points that do not return a status
 
 _lib = None
 
@@ -225,6 +229,8 @@ def load():
     lib.pf_vit_attention_rpb_bf16_lds_bytes.argtypes = [ci, ci, ci]
     lib.pf_conv_last_variant.restype = ci                             # variant code of the thread's last pf_conv launch, not a status
     lib.pf_conv_last_variant.argtypes = []
+    lib.pf_pngd_par_window.restype = ci                               # lanes per window of the subsequence inflate, not a status
+    lib.pf_pngd_par_window.argtypes = []
     _lib = lib
     return lib
 

@@ -224,4 +224,106 @@ inline int inflate_model(const uint8_t* deflate, long n, long expected, uint32_t
   return 0;
 }
 
+// ---- the subsequence decode of csrc/png_inflate_par.hip in plain loops: the same lane decoder through the same round schedule
+struct ParWindowHost {
+  uint32_t entry[PAR_WINDOW];
+  int live;               // the places of the window that are lanes
+  Lane lane[PAR_WINDOW], prev[PAR_WINDOW];
+};
+
+// The rounds of the window whose first lane is `first` and whose lane 0 enters at `carry` -> the number of rounds in which a lane changed
+inline uint32_t par_rounds(Bits& b, ParWindowHost& w, uint32_t first, uint32_t carry, uint32_t stop, uint32_t S, const Code& lit, const Code& dist) {
+  NullSink null;
+  const int live = w.live = lanes_in_window(first, S, stop);
+  for (int k = 0; k < PAR_WINDOW; ++k) {
+    w.entry[k] = k == 0 ? carry : (first + (uint32_t)k) * S;
+    w.lane[k] = k < live ? decode_lane(b, w.entry[k], lane_end(first + (uint32_t)k, S, stop), lit, dist, null) : Lane{w.entry[k], 0u, 0u, 0u, S_OK};
+  }
+  uint32_t rounds = 0;
+  for (int r = 1; r < live; ++r) {
+    memcpy(w.prev, w.lane, sizeof(w.prev));           // a round reads only the round before
+    bool changed = false;
+    for (int k = 1; k < live; ++k) {
+      if ((w.prev[k - 1].flags & L_EOB) || w.prev[k - 1].exit == w.entry[k]) continue;
+      w.entry[k] = w.prev[k - 1].exit;
+      w.lane[k] = decode_lane(b, w.entry[k], lane_end(first + (uint32_t)k, S, stop), lit, dist, null);
+      changed = true;
+    }
+    if (!changed) break;
+    rounds = (uint32_t)r;
+  }
+  return rounds;
+}
+
+// first lane with L_EOB, with L_INVALID, and whose running total (from `total`) exceeds `expected`
+inline void par_firsts(const ParWindowHost& w, uint64_t total, uint64_t expected, int& e, int& fi, int& fs) {
+  e = fi = fs = PAR_WINDOW;
+  for (int k = 0; k < PAR_WINDOW; ++k) {
+    total += w.lane[k].bytes;
+    if (e == PAR_WINDOW && (w.lane[k].flags & L_EOB)) e = k;
+    if (fi == PAR_WINDOW && (w.lane[k].flags & L_INVALID)) fi = k;
+    if (fs == PAR_WINDOW && total > expected) fs = k;
+  }
+}
+
+// scan_block with the symbols decoded in subsequences of S bits: the same record where scan_block's status is S_OK, some other status
+// elsewhere.  -> the largest number of rounds a window needed
+inline uint32_t scan_block_par(Bits b, uint32_t start, uint32_t max_bits, uint32_t expected, uint32_t S, HostCodes& hc, ParWindowHost& w, uint32_t* rec) {
+  uint32_t p = start, rounds = 0;
+  const uint32_t bfinal = peek(b, p) & 1u;
+  uint64_t total = 0;
+  int st = start < b.nbits ? read_block_codes(b, p, hc.lens, hc.lit(), hc.dist(), hc.offs) : S_EOS;
+  if (st == S_OK) {
+    const uint32_t stop = scan_stop(b, start, max_bits), j0 = p / S;
+    st = stop >= b.nbits ? S_EOS : S_LIMIT;
+    for (uint32_t first = j0; (uint64_t)first * S < stop; first += PAR_WINDOW) {
+      const uint32_t r = par_rounds(b, w, first, p, stop, S, hc.lit(), hc.dist());
+      if (r > rounds) rounds = r;
+      int e, fi, fs, how;
+      par_firsts(w, total, expected, e, fi, fs);
+      const int at = chain_event(e, fi, fs, how);
+      for (int k = 0; k < PAR_WINDOW && k <= at; ++k) total += w.lane[k].bytes;
+      if (at < PAR_WINDOW) {
+        const bool eob = how == S_OK;
+        p = eob ? w.lane[at].eob : w.lane[at].exit;
+        st = eob ? (p > b.nbits ? S_EOS : S_OK) : how;
+        break;
+      }
+      p = w.lane[w.live - 1].exit;
+    }
+  }
+  rec[0] = start;
+  rec[1] = p;
+  rec[2] = total > 0xffffffffull ? 0xffffffffu : (uint32_t)total;
+  rec[3] = (uint32_t)st | (bfinal << 8);
+  return rounds;
+}
+
+// The inflate pass of one fixed or dynamic block {start, type, offset, bytes}: the rounds, then every lane of the true chain decodes once
+// more from its final entry into lit / ref, RefSink with `base` at the lane's own first output byte.  -> PF_PNGD_F_* flags
+inline uint32_t inflate_block_par(Bits b, const uint32_t* blk, uint32_t S, HostCodes& hc, ParWindowHost& w, uint8_t* lit, uint32_t* ref, uint32_t* rounds) {
+  uint32_t p = blk[0], flags = 0;
+  const uint32_t off = blk[2], end = blk[2] + blk[3];
+  if (read_block_codes(b, p, hc.lens, hc.lit(), hc.dist(), hc.offs) != S_OK) return PF_PNGD_F_STREAM;
+  uint64_t total = 0;
+  for (uint32_t first = p / S; (uint64_t)first * S < b.nbits; first += PAR_WINDOW) {
+    const uint32_t r = par_rounds(b, w, first, p, b.nbits, S, hc.lit(), hc.dist());
+    if (r > *rounds) *rounds = r;
+    int e, fi, fs;
+    par_firsts(w, 0, ~0ull, e, fi, fs);
+    for (int k = 0; k < PAR_WINDOW && k <= e; ++k) {
+      const uint64_t at = (uint64_t)off + total;
+      const uint32_t o = at < end ? (uint32_t)at : end;
+      RefSink sink{lit, ref, o, o, end};
+      const Lane l = decode_lane(b, w.entry[k], lane_end(first + (uint32_t)k, S, b.nbits), hc.lit(), hc.dist(), sink);
+      if (l.sink == S_DIST) flags |= PF_PNGD_F_DISTANCE;
+      else if (l.sink != S_OK || (l.flags & L_INVALID)) flags |= PF_PNGD_F_STREAM;
+      total += w.lane[k].bytes;
+    }
+    if (e < PAR_WINDOW) return (uint64_t)off + total == end ? flags : flags | PF_PNGD_F_STREAM;
+    p = w.lane[w.live - 1].exit;
+  }
+  return flags | PF_PNGD_F_STREAM;            // the stream ended in front of the end-of-block code
+}
+
 }  // namespace pf_pngd

@@ -369,4 +369,106 @@ PF_PNGD_HD void scan_block(Bits b, uint32_t start, uint32_t max_bits, uint32_t e
   rec[3] = (uint32_t)st | (bfinal << 8);
 }
 
+// ---- decoding inside a block in parallel subsequences (csrc/png_inflate_par.hip on the device, png_host.h on the host)
+//
+// The stream is cut into lanes, the absolute bit ranges [jS, (j + 1)S).  A lane decodes from an entry bit, taken to be the start of a
+// literal/length code, the tokens that start in front of its end; its exit is the start of the first token at or behind the end, which
+// is the next lane's true entry.  A block is worked through in windows of PAR_WINDOW lanes: lane 0 of a window starts from the known
+// entry, every other lane first guesses its own jS, and in each round a lane whose predecessor's exit of the round before differs from
+// its entry decodes again from that exit (a lane behind an end-of-block code is left as it is).  Lane k is final after round k, so the
+// rounds of a window are at most PAR_WINDOW - 1 and end sooner when none changed.  Bounds: a lane turns only while p < end <= nbits and
+// every turn consumes at least one bit (an invalid code exactly one), so a lane is bounded by end - entry.
+#ifndef PF_PNGD_PAR_WINDOW
+// lanes per window = threads per workgroup of the two kernels; the host models use the same number.  512 had the lowest whole-decode
+// median on the two RGB level-6 files of profiles/png_inflate_par_time.json (5.11 + 16.35 ms against 4.93 + 16.68 ms with 1024 threads
+// and 5.26 + 16.26 ms with 256)
+#define PF_PNGD_PAR_WINDOW 512
+#endif
+constexpr int PAR_WINDOW = PF_PNGD_PAR_WINDOW;
+constexpr uint32_t PAR_MIN_BITS = 64, PAR_MAX_BITS = 1u << 16;        // a lane's length: a multiple of 32 in this range
+
+PF_PNGD_HD bool par_bits_ok(uint32_t s) { return s >= PAR_MIN_BITS && s <= PAR_MAX_BITS && (s & 31u) == 0; }
+
+enum { L_EOB = 1, L_INVALID = 2 };
+struct Lane {
+  uint32_t exit;          // the start of the first token at or behind the lane's end (behind the end-of-block code when one was read)
+  uint32_t bytes;         // output bytes of the lane's tokens: below 2^24 (at most 2^15 matches of 258 bytes in 2^16 bits)
+  uint32_t eob;           // the bit behind the end-of-block code, when L_EOB is set
+  uint32_t flags;         // L_EOB; L_INVALID: an invalid code, a length symbol above 285, a distance symbol above 29, or a token that
+                          // runs past the end of the stream
+  int sink;               // S_OK, or the status with which the sink refused a token (the lane ends there)
+};
+
+// The tokens that start in [p, end), end <= b.nbits.  A literal is one token; a length, its extra bits, the distance code and its extra
+// bits are one token.  An invalid code consumes one bit and produces nothing; an end-of-block code ends the lane; p >= end produces
+// nothing and passes p on.  The sink takes literal(byte) -> bool and match(length, distance) -> status, as in decode_symbols.
+template <class Sink>
+PF_PNGD_HD Lane decode_lane(Bits& b, uint32_t p, uint32_t end, const Code& lit, const Code& dist, Sink& out) {
+  Lane r{p, 0u, 0u, 0u, S_OK};
+  while (p < end) {
+    const uint32_t token = p;
+    int s = decode_sym(b, p, lit);
+    if (s >= 0 && s < 256) {
+      if (!out.literal((uint8_t)s)) { r.sink = S_SIZE; break; }
+      ++r.bytes;
+      continue;
+    }
+    if (s == 256) {
+      r.flags |= L_EOB;
+      r.eob = p;
+      break;
+    }
+    s -= 257;
+    if (s >= 0 && s <= 28) {
+      int base, extra;
+      length_code(s, base, extra);
+      const int len = base + (int)(peek(b, p) & ((1u << extra) - 1u));
+      p += extra;
+      const int d = decode_sym(b, p, dist);
+      if (d >= 0 && d <= 29) {
+        distance_code(d, base, extra);
+        const uint32_t back = (uint32_t)base + (peek(b, p) & ((1u << extra) - 1u));
+        p += extra;
+        if (p > b.nbits) { r.flags |= L_INVALID; break; }
+        const int st = out.match((uint32_t)len, back);
+        if (st != S_OK) { r.sink = st; break; }
+        r.bytes += (uint32_t)len;
+        continue;
+      }
+    }
+    r.flags |= L_INVALID;
+    p = token + 1;
+  }
+  r.exit = p;
+  return r;
+}
+
+struct NullSink {         // the rounds: only the lane's exit and byte count matter
+  PF_PNGD_HD bool literal(uint8_t) { return true; }
+  PF_PNGD_HD int match(uint32_t, uint32_t) { return S_OK; }
+};
+
+// lane j of a stream cut every S bits, clipped to `stop`
+PF_PNGD_HD uint32_t lane_end(uint32_t j, uint32_t S, uint32_t stop) {
+  const uint64_t e = ((uint64_t)j + 1u) * S;
+  return e < stop ? (uint32_t)e : stop;
+}
+// How many of the window's PAR_WINDOW places, from lane `first` (first * S < stop) on, are lanes: those that begin in front of `stop`.
+// The places behind them hold nothing and take no part in the rounds.
+PF_PNGD_HD int lanes_in_window(uint32_t first, uint32_t S, uint32_t stop) {
+  const uint32_t n = (stop - 1u) / S + 1u - first;
+  return n < (uint32_t)PAR_WINDOW ? (int)n : PAR_WINDOW;
+}
+
+// What the true chain of a window comes to: lanes 0, 1, ... up to the first that read an end-of-block code.  e, fi, fs: the first lane
+// with L_EOB, with L_INVALID, and whose running output total exceeds `expected` (PAR_WINDOW when there is none).  -> the lane at which
+// the block's decode ends (PAR_WINDOW: it goes on behind the window's last lane) and in `st` how: an invalid code counts in front of a size
+// overflow in the same lane, and both in front of the end-of-block code.
+PF_PNGD_HD int chain_event(int e, int fi, int fs, int& st) {
+  st = S_OK;
+  if (fi < PAR_WINDOW && fi <= e && fi <= fs) { st = S_INVALID; return fi; }
+  if (fs < PAR_WINDOW && fs <= e) { st = S_SIZE; return fs; }
+  return e;
+}
+
 }  // namespace pf_pngd

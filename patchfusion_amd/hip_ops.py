@@ -1419,6 +1419,28 @@ class HipOps:
               "pf_pngd_inflate")
 
     @staticmethod
+    def pngd_scan_par(words, nbits, starts, n, max_block_bits, expected, subsequence_bits, records, max_rounds):
+        """pngd_scan with the symbols of a block decoded in lanes of subsequence_bits bits (png_inflate_par.hip): the same records wherever
+        pngd_scan's status is OK; max_rounds int32 [1] (zeroed by the caller) is raised to the largest number of rounds a window needed"""
+        assert words.dtype == torch.int32 and starts.dtype == torch.int32 and records.dtype == torch.int32
+        assert words.is_contiguous() and starts.is_contiguous() and records.is_contiguous() and 0 < nbits <= 32 * (words.numel() - 2)
+        assert 0 <= n <= starts.numel() and records.numel() >= 4 * n and max_rounds.dtype == torch.int32 and max_rounds.numel() >= 1
+        check(_L.pf_pngd_scan_par(_p(words), words.numel(), int(nbits), _p(starts), int(n), int(max_block_bits), int(expected), int(subsequence_bits),
+                                  _p(records), _p(max_rounds), _stream()), "pf_pngd_scan_par")
+        return records
+
+    @staticmethod
+    def pngd_inflate_par(words, nbits, blocks, expected, subsequence_bits, lit, ref, status, max_rounds):
+        """pngd_inflate with one workgroup per block and one lane of subsequence_bits bits per thread; afterwards a reference points to a literal
+        or into a strictly earlier lane's range"""
+        assert words.dtype == torch.int32 and blocks.dtype == torch.int32 and lit.dtype == torch.uint8 and ref.dtype == torch.int32
+        assert all(t.is_contiguous() for t in (words, blocks, lit, ref)) and 0 < nbits <= 32 * (words.numel() - 2)
+        assert blocks.dim() == 2 and blocks.shape[1] == 4 and lit.numel() == expected and ref.numel() == expected
+        assert status.dtype == torch.int32 and status.numel() >= 1 and max_rounds.dtype == torch.int32 and max_rounds.numel() >= 1
+        check(_L.pf_pngd_inflate_par(_p(words), words.numel(), int(nbits), _p(blocks), blocks.shape[0], int(expected), int(subsequence_bits), _p(lit),
+                                     _p(ref), _p(status), _p(max_rounds), _stream()), "pf_pngd_inflate_par")
+
+    @staticmethod
     def pngd_resolve(lit, ref, rounds, out):
         """`rounds` pointer-jumping launches over ref (in place), then out[i] = lit[ref[i]]"""
         assert lit.dtype == torch.uint8 and ref.dtype == torch.int32 and out.dtype == torch.uint8

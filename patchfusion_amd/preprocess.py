@@ -402,6 +402,20 @@ def _decode_jpeg_progressive(host, ops, dev, entropy, apply_orientation, S, cap)
 PNG_MAX_BLOCK_BITS = 1 << 21
 PNG_MAX_CHAIN_ROUNDS = 8
 PNG_INFLATE = "host"
+# block_decode='subsequences' (opt-in, csrc/png_inflate_par.hip): a block goes to one workgroup of PNG_PAR_WINDOW threads and every thread
+# decodes one lane of subsequence_bits bits of it.  PNG_PAR_WINDOW restates PF_PNGD_PAR_WINDOW of csrc/png_inflate.h (the library
+# answers pf_pngd_par_window()).  Both numbers were chosen by tools/png_decode_time.py --subsequences (profiles/png_inflate_par_time.json,
+# one MI355X) with the rule "lowest sum of the whole-decode medians on the two RGB level-6 files (2048x1024 + 3840x2160)".  Workgroup
+# size at 256-bit lanes: 1024 threads 4.93 + 16.68 = 21.61 ms, 512 threads 5.11 + 16.35 = 21.46 ms, 256 threads 5.26 + 16.26 = 21.52 ms
+# (1024 is faster at the small file and slower at the large one, whose 759 workgroups then do not fit the device at once).  Lane length
+# at 512 threads: 128 bits 21.46 ms, 256 bits 21.46 ms, 512 bits 21.44 ms, 1024 bits 22.03 ms: the first three are level inside the
+# min-max spread (0.1 - 0.5 ms), and 256 is also level with the best on the other six files of the table, where 128 loses up to 0.9 ms
+# (level-1 files, 12 - 17 rounds).  The mode's scan + inflate stages take 0.8 and 1.1 ms against the sequential arm's 14.4 and 15.5 ms,
+# and the whole decode beats inflate='host' at both sizes (5.1 against 16.8 ms, 16.4 against 76.8 ms); the defaults above are left as
+# they are on purpose.
+PNG_BLOCK_DECODE = "sequential"
+PNG_SUBSEQUENCE_BITS = 256
+PNG_PAR_WINDOW = 512
 PNG_S_OK, PNG_S_INVALID, PNG_S_LIMIT, PNG_S_EOS, PNG_S_SIZE, PNG_S_DIST = range(6)       # PF_PNGD_S_* of pf_hip.h
 PNG_F_STREAM, PNG_F_DISTANCE, PNG_F_FILTER, PNG_F_PLTE = 1, 2, 4, 8                    # PF_PNGD_F_*
 PNG_PAD_WORDS = 2                                                                      # PF_PNGD_PAD_WORDS
@@ -566,12 +580,25 @@ class PngChain:
         return None
 
 
-def png_inflate_device(host, ops, dev, max_chain_rounds, max_block_bits, timing=None):
+def _png_subsequence_bits(value):
+    bits = PNG_SUBSEQUENCE_BITS if value is None else value
+    if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or bits < 64 or bits > (1 << 16) or bits % 32:
+        raise ValueError(f"subsequence_bits must be a multiple of 32 in 64 .. 2^16, got {value!r}")
+    return int(bits)
+
+
+def png_inflate_device(host, ops, dev, max_chain_rounds, max_block_bits, timing=None, block_decode="sequential", subsequence_bits=None):
     """the device inflate of decode_png on a PngHost -> (inflated uint8 [height * (1 + rowbytes)] on the device or None, stats).  None:
     stats['fallback_reason'] says what only the host arm can complete; nothing was decoded.  The stream's own errors raise.
     timing: a dict that receives the seconds of 'finder', 'scan', 'chain_walk' (with its copies), 'inflate' and 'resolve'; each part then
-    ends in a synchronise, which the untimed path does not do."""
+    ends in a synchronise, which the untimed path does not do.
+    block_decode='subsequences' runs the scan and inflate passes of csrc/png_inflate_par.hip with lanes of subsequence_bits bits; the
+    stats then carry 'sync_rounds' as a device word until decode_png reads it back with the status."""
     import time
+    if block_decode not in ("sequential", "subsequences"):
+        raise ValueError(f"block_decode must be 'sequential' or 'subsequences', got {block_decode!r}")
+    par = block_decode == "subsequences"
+    S = _png_subsequence_bits(subsequence_bits) if par else None
     h = host.header
     n, expected = host.deflate.size, h.inflated_bytes
     stats = dict(candidates=0, chain_rounds=0, resolve_rounds=0, blocks=None, bytes_uploaded=0, bytes_downloaded=0, fallback_reason=None, adler=None)
@@ -611,11 +638,16 @@ def png_inflate_device(host, ops, dev, max_chain_rounds, max_block_bits, timing=
         return give_up("the candidate list overflowed")
     chain = PngChain(host)
     starts, nstart = cand, ncand
+    if par:
+        stats["sync_rounds"] = torch.zeros(1, dtype=torch.int32, device=dev)
     while True:
         stats["chain_rounds"] += 1
         if nstart:
             records = torch.empty((nstart, 4), dtype=torch.int32, device=dev)
-            ops.pngd_scan(words, nbits, starts, nstart, max_block_bits, min(expected, 0xffffffff), records)
+            if par:
+                ops.pngd_scan_par(words, nbits, starts, nstart, max_block_bits, min(expected, 0xffffffff), S, records, stats["sync_rounds"])
+            else:
+                ops.pngd_scan(words, nbits, starts, nstart, max_block_bits, min(expected, 0xffffffff), records)
             tick("scan")
             chain.add(records.cpu().numpy())
             stats["bytes_downloaded"] += 16 * nstart
@@ -639,15 +671,22 @@ def png_inflate_device(host, ops, dev, max_chain_rounds, max_block_bits, timing=
     lit = torch.empty(expected, dtype=torch.uint8, device=dev)
     ref = torch.empty(expected, dtype=torch.int32, device=dev)
     stats["status"] = torch.zeros(1, dtype=torch.int32, device=dev)
-    ops.pngd_inflate(words, nbits, blocks, expected, lit, ref, stats["status"])
+    units = len(chain.blocks)
+    if par:
+        ops.pngd_inflate_par(words, nbits, blocks, expected, S, lit, ref, stats["status"], stats["sync_rounds"])
+        # a reference now points into an earlier lane's range: the lanes a block's bits touch (from its header on, so never too few)
+        units = sum(1 if kind == 0 else (chain.table[p][0] + S - 1) // S - p // S for p, kind, _, _ in chain.blocks)
+    else:
+        ops.pngd_inflate(words, nbits, blocks, expected, lit, ref, stats["status"])
     tick("inflate")
-    stats["resolve_rounds"] = max(len(chain.blocks) - 1, 0).bit_length() + 1          # ceil(log2(blocks)) + 1
+    stats["resolve_rounds"] = max(units - 1, 0).bit_length() + 1                      # ceil(log2(blocks or lane ranges)) + 1
     inflated = ops.pngd_resolve(lit, ref, stats["resolve_rounds"], torch.empty(expected, dtype=torch.uint8, device=dev))
     tick("resolve")
     return inflated, stats
 
 
-def decode_png(data, device="cuda", inflate=None, verify=True, max_chain_rounds=None, max_block_bits=None, ops=None, timing=None):
+def decode_png(data, device="cuda", inflate=None, verify=True, max_chain_rounds=None, max_block_bits=None, ops=None, timing=None,
+               block_decode=None, subsequence_bits=None):
     """PNG (bytes or a path) -> (device tensor, PngInfo), lossless and bit-exact with the PNG specification: uint8 or torch.uint16 (native
     byte order), [H,W] for grey, [H,W,2] grey+alpha, [H,W,3] RGB, [H,W,4] RGBA.  A palette expands to uint8 [H,W,3] (tRNS is ignored and
     reported as info.has_trns); grey of 1 / 2 / 4 bits expands to uint8 by bit replication (x255, x85, x17) as libpng's
@@ -655,7 +694,10 @@ def decode_png(data, device="cuda", inflate=None, verify=True, max_chain_rounds=
     inflate='device' uploads the compressed stream and inflates it block-parallel on the GPU; 'host' runs the standard library's zlib and
     uploads the filtered bytes; unfilter, expansion and the Adler-32 are the same device code either way, and so are the pixels.  When the
     device arm gives up (candidate list overflow, a block above max_block_bits, more fixed blocks than max_chain_rounds scan passes) the
-    host arm completes the file: info.inflate and info.fallback_reason say so.  verify=True checks the Adler-32 (computed on the device),
+    host arm completes the file: info.inflate and info.fallback_reason say so.  block_decode='subsequences' (with inflate='device'
+    only) decodes inside a block in parallel, every thread of a workgroup one lane of subsequence_bits bits (a multiple of 32 in
+    64 .. 2^16, default PNG_SUBSEQUENCE_BITS); info.sync_rounds is the largest number of rounds a window of lanes needed to agree
+    (0 for 'sequential').  verify=True checks the Adler-32 (computed on the device),
     verify='full' also the CRC-32 of the IDAT chunks (on the host: one more pass over the compressed bytes), verify=False neither.
     Unsupported or broken files raise a PngError subclass (a ValueError); there is no fallback to a host image library."""
     inflate = PNG_INFLATE if inflate is None else inflate
@@ -663,6 +705,12 @@ def decode_png(data, device="cuda", inflate=None, verify=True, max_chain_rounds=
         raise ValueError(f"inflate must be 'device' or 'host', got {inflate!r}")
     if verify not in (True, False, "full"):
         raise ValueError(f"verify must be True, False or 'full', got {verify!r}")
+    block_decode = PNG_BLOCK_DECODE if block_decode is None else block_decode
+    if block_decode not in ("sequential", "subsequences"):
+        raise ValueError(f"block_decode must be 'sequential' or 'subsequences', got {block_decode!r}")
+    if block_decode == "subsequences" and inflate != "device":
+        raise ValueError("block_decode='subsequences' needs inflate='device'")
+    lane_bits = _png_subsequence_bits(subsequence_bits)
     rounds_cap = PNG_MAX_CHAIN_ROUNDS if max_chain_rounds is None else int(max_chain_rounds)
     bits_cap = PNG_MAX_BLOCK_BITS if max_block_bits is None else int(max_block_bits)
     if rounds_cap < 0:
@@ -687,10 +735,11 @@ def decode_png(data, device="cuda", inflate=None, verify=True, max_chain_rounds=
     used, inflated, stated = inflate, None, None
     stats = dict(candidates=0, chain_rounds=0, resolve_rounds=0, blocks=None, bytes_uploaded=0, bytes_downloaded=0, fallback_reason=None)
     if inflate == "device":
-        inflated, stats = png_inflate_device(host, ops, dev, rounds_cap, bits_cap, timing)
+        inflated, stats = png_inflate_device(host, ops, dev, rounds_cap, bits_cap, timing, block_decode, lane_bits)
         stated = stats.get("adler")
         if inflated is None:
             used = "host"
+            stats.pop("sync_rounds", None)
     if used == "host":
         t0 = time.perf_counter()
         raw, stated = host.inflate()
@@ -699,10 +748,13 @@ def decode_png(data, device="cuda", inflate=None, verify=True, max_chain_rounds=
         if timing is not None:
             timing["host_inflate"] = time.perf_counter() - t0
     t0 = time.perf_counter()
-    result = torch.zeros(2, dtype=torch.int32, device=dev)             # {Adler-32, status flags}: the one 8-byte copy back
-    status = result[1:]
+    # {Adler-32, status flags} and, behind a subsequence decode, its sync rounds: the one 8- or 12-byte copy back
+    result = torch.zeros(3 if "sync_rounds" in stats else 2, dtype=torch.int32, device=dev)
+    status = result[1:2]
     if "status" in stats:
         status.copy_(stats.pop("status"))
+    if "sync_rounds" in stats:
+        result[2:].copy_(stats.pop("sync_rounds"))
     if verify:
         ops.pngd_adler(inflated, torch.empty(2, dtype=torch.int64, device=dev), result)
         if timing is not None and dev.type == "cuda":
@@ -722,7 +774,7 @@ def decode_png(data, device="cuda", inflate=None, verify=True, max_chain_rounds=
             stats["bytes_uploaded"] += 768
         ops.pngd_expand(h, recon, palette, image, status)
     got = result.cpu().numpy().view(np.uint32)
-    stats["bytes_downloaded"] += 8
+    stats["bytes_downloaded"] += 4 * got.size
     if timing is not None:
         timing["unfilter_expand"] = time.perf_counter() - t0
     flags = int(got[1])
@@ -734,7 +786,9 @@ def decode_png(data, device="cuda", inflate=None, verify=True, max_chain_rounds=
     info = PngInfo(width=W, height=H, bit_depth=h.depth, color_type=h.color_type, channels=h.channels, has_trns=bool(h.has_trns),
                    inflate=used, fallback_reason=stats["fallback_reason"], blocks=stats["blocks"], candidates=stats["candidates"],
                    chain_rounds=stats["chain_rounds"], resolve_rounds=stats["resolve_rounds"], compressed_bytes=int(h.compressed_bytes),
-                   bytes_uploaded=stats["bytes_uploaded"], bytes_downloaded=stats["bytes_downloaded"])
+                   bytes_uploaded=stats["bytes_uploaded"], bytes_downloaded=stats["bytes_downloaded"],
+                   block_decode=block_decode if used == "device" else "sequential", subsequence_bits=lane_bits,
+                   sync_rounds=int(got[2]) if got.size > 2 else 0)
     return image, info
 
 
