@@ -733,6 +733,40 @@ int pf_pngd_scan_par(const uint32_t* words, long nwords, uint32_t nbits, const u
 int pf_pngd_inflate_par(const uint32_t* words, long nwords, uint32_t nbits, const uint32_t* blocks, int nblocks, uint32_t expected,
                         uint32_t subsequence_bits, uint8_t* lit, uint32_t* ref, uint32_t* status, uint32_t* max_rounds, void* stream);
 
+/* ---------------------------------------------------------------- ground-truth depth files of the evaluation loop (csrc/gtread.hip):
+ * estimator/datasets/general_dataset.py:60-143 (DepthMap) and u4k_dataset.py:118-119,168.  `src` is the PAYLOAD of the file as it lies
+ * on disk, uploaded from the payload's offset (so it starts at the first sample, aligned to the sample's size; 16-byte alignment selects
+ * the wide loads), or the uint8 / uint16 image pf_pngd_expand made.  One launch writes depth [H][W] float32 and, when edge_src is not
+ * null, the plane the reference passes to get_boundaries (feed it to pf_depth_boundaries).  x = float32(sample); a and b are float32
+ * constants the HOST has rounded the way numpy rounds a Python float that meets a float32 array; every +, - and / is one correctly
+ * rounded float32 operation, denormals kept:
+ *   mode                kinds              depth                                                     edge source            a, b
+ *   PF_GT_U4K           F16 F32 F64        a / x                                                     x                      depth factor, -
+ *   PF_GT_MID           F32                (a / (x + b)) / 1000, then 0 where x == +inf              x with +inf -> 0       f * baseline, doffs
+ *   PF_GT_ETH3D         F32 (no swap)      x with NaN, +inf, -inf -> 0                               = depth                -, -
+ *   PF_GT_GTA           U8 U16             x / 256                                                   = depth                -, -
+ *   PF_GT_CITYSCAPES    U8 U16             d = x > 0 ? (x - 1) / 256 : 0;  a / d, NaN, +-inf -> 0    = depth                0.209313 * 2262.52, -
+ *   PF_GT_RAW           F16 F32 F64        x (read_pfm, read_npy; W = width * 3 for a colour PFM)    = depth                -, -
+ * Only +inf is masked in PF_GT_MID: -inf and NaN come out as the arithmetic gives them (-0.0 and NaN), as in the reference.
+ * flags: PF_GT_SWAP = the samples are big-endian (float kinds only), PF_GT_FLIP = output row y reads source row H - 1 - y (PFM stores
+ * the bottom row first).  Refused (PF_ERR_ARG): null src or depth, H or W <= 0, H * W >= 2^31, an unknown kind, mode or flag, a kind /
+ * mode / swap combination the table does not have, src not aligned to its sample, depth or edge_src not 16-byte aligned.  src must hold
+ * H * W samples; no plane may overlap another. */
+#define PF_GT_F16 0
+#define PF_GT_F32 1
+#define PF_GT_F64 2
+#define PF_GT_U8 3
+#define PF_GT_U16 4
+#define PF_GT_U4K 0
+#define PF_GT_MID 1
+#define PF_GT_ETH3D 2
+#define PF_GT_GTA 3
+#define PF_GT_CITYSCAPES 4
+#define PF_GT_RAW 5
+#define PF_GT_SWAP 1
+#define PF_GT_FLIP 2
+int pf_gt_convert(const void* src, int kind, int flags, int mode, int H, int W, float a, float b, float* depth, float* edge_src, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

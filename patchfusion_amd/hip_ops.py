@@ -1485,5 +1485,28 @@ class HipOps:
         check(_L.pf_pngd_to_rgb8(_p(image), H, W, ch, 8 * image.element_size(), _p(rgb), _stream()), "pf_pngd_to_rgb8")
         return rgb
 
+    # ---------------- ground-truth depth files (gtread.hip) ----------------
+    GT_KINDS = {"f2": 0, "f4": 1, "f8": 2, "u1": 3, "u2": 4}                       # PF_GT_F16 .. PF_GT_U16
+    GT_KIND_BYTES = {"f2": 2, "f4": 4, "f8": 8, "u1": 1, "u2": 2}
+    GT_MODES = {"u4k": 0, "mid": 1, "eth3d": 2, "gta": 3, "cityscapes": 4, "raw": 5}   # PF_GT_U4K .. PF_GT_RAW
+    GT_SWAP, GT_FLIP = 1, 2
+
+    @staticmethod
+    def gt_convert(src, kind, mode, H, W, a, b, depth, edge_src=None, swap=False, flip=False):
+        """The payload of a ground-truth file (src: the bytes as uint8, or a decoded uint8 / uint16 image; H * W samples of `kind` =
+        'f2' 'f4' 'f8' 'u1' 'u2') -> depth float32 [H,W] and, when given, the plane get_boundaries takes; the arithmetic per `mode` is
+        the table of include/pf_hip.h.  a, b: the mode's constants, rounded to float32 on the way in."""
+        if kind not in HipOps.GT_KINDS or mode not in HipOps.GT_MODES:
+            raise ValueError(f"gt_convert: unknown kind {kind!r} or mode {mode!r}")
+        H, W = int(H), int(W)
+        assert src.is_contiguous() and src.numel() * src.element_size() == H * W * HipOps.GT_KIND_BYTES[kind], "payload size"
+        for t in (depth, edge_src):
+            assert t is None or (t.dtype == torch.float32 and tuple(t.shape) == (H, W) and t.is_contiguous())
+        assert edge_src is None or edge_src.data_ptr() != depth.data_ptr()
+        flags = (HipOps.GT_SWAP if swap else 0) | (HipOps.GT_FLIP if flip else 0)
+        check(_L.pf_gt_convert(_p(src), HipOps.GT_KINDS[kind], flags, HipOps.GT_MODES[mode], H, W, float(a), float(b), _p(depth), _p(edge_src),
+                               _stream()), "pf_gt_convert")
+        return depth
+
 
 ops = HipOps()
