@@ -767,6 +767,36 @@ int pf_pngd_inflate_par(const uint32_t* words, long nwords, uint32_t nbits, cons
 #define PF_GT_FLIP 2
 int pf_gt_convert(const void* src, int kind, int flags, int mode, int H, int W, float a, float b, float* depth, float* edge_src, void* stream);
 
+/* ---------------------------------------------------------------- training-side augmentations of UnrealStereo4kDataset (csrc/augment.hip):
+ * estimator/datasets/u4k_dataset.py:121-134 with transformers/augmentations.py (aug_rotate, aug_color, aug_flip).  The HOST draws every
+ * random number and builds the matrix; both entry points are pure functions of their arguments.  m and colour (and a below) are HOST
+ * arrays, read before the call returns.
+ *
+ * pf_aug_image_u8_to_f32: img uint8 [H][W][3] in the raw file's order (B, G, R) -> out float32 [3][H][W] (R, G, B).  Output (y, x)
+ * is Image.rotate(angle, resample=BILINEAR) of Pillow at (flip ? W - 1 - x : x, y), bit for bit: with m[6] the matrix Image.rotate
+ * builds (angle % 360, a = -radians(angle), cos and sin rounded to 15 decimals, centre (W/2, H/2)), in double and without contraction
+ *   xs = m0 (x + 0.5) + m1 (y + 0.5) + m2,  ys = m3 (x + 0.5) + m4 (y + 0.5) + m5;  0 if xs < 0 || xs >= W || ys < 0 || ys >= H;
+ *   xin = xs - 0.5, x0 = floor(xin), dx = xin - x0 (the same in y); columns x0 and x0 + 1 clamped to [0, W - 1], row y0 clamped, row
+ *   y0 + 1 only if inside the image (else v2 = v1); every blend a + (b - a) d, along x then along y; truncated to a byte.
+ * Then numpy's float32 arithmetic: v = float32(byte) / 255.0f and, if colour_on,
+ *   v = float32(pow(double(v), double(gamma)));  v = v * brightness;  v = float32(double(v) * colour[c]);  v = min(max(v, 0), 1)
+ * with gamma and brightness already rounded to float32 by the host and colour[c] indexed by the OUTPUT channel (R, G, B).  numpy's
+ * float32 `**` differs from the correctly rounded power in its last bit at some operands, so with colour_on the result is within one
+ * float32 rounding per step of the exact chain rather than equal to numpy's; without it the plane equals the reference bit for bit.
+ * Refused (PF_ERR_ARG): null img, out or m (or colour with colour_on), H or W <= 0, H * W >= 2^31, a matrix entry that is not finite,
+ * out not 16-byte aligned, img and out overlapping.
+ *
+ * pf_aug_planes_nearest: src0 (and src1, or null with dst1 null) float32 [H][W] -> dst0 (dst1): Image.rotate(angle, resample=NEAREST)
+ * on a mode 'F' image, Pillow's 16.16 fixed-point path, then the flip.  a[6] = FIX(m0), FIX(m1), FIX(m2 + m0 / 2 + m1 / 2), FIX(m3),
+ * FIX(m4), FIX(m5 + m3 / 2 + m4 / 2) with FIX(v) = floor(v * 65536 + 0.5); for x' = flip ? W - 1 - x : x the source is
+ *   sx = (a2 + x' a0 + y a1) >> 16,  sy = (a5 + x' a3 + y a4) >> 16   (64-bit sums, arithmetic shift)
+ * and the output is 0 where (sx, sy) is outside the plane -- for the depth plane too (not factor / 0).
+ * Refused (PF_ERR_ARG): null src0, dst0 or a, exactly one of src1 / dst1 null, H or W <= 0, H * W >= 2^31, a destination not 16-byte
+ * aligned, any two of the planes overlapping. */
+int pf_aug_image_u8_to_f32(const unsigned char* img, int H, int W, const double* m, int flip, int colour_on, float gamma, float brightness,
+                           const double* colour, float* out, void* stream);
+int pf_aug_planes_nearest(const float* src0, const float* src1, int H, int W, const int* a, int flip, float* dst0, float* dst1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 _EXPORTS = {"read_depth_gt": "groundtruth", "read_pfm": "groundtruth", "read_npy": "groundtruth", "GtError": "groundtruth",
-            "ImageDataset": "datasets"}
+            "ImageDataset": "datasets", "UnrealStereo4kDataset": "datasets", "collate_train": "datasets"}
 
 
 def __getattr__(name):          # resolved on first use: importing the package stays free of torch and of the HIP library

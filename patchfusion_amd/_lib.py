@@ -184,6 +184,9 @@ SIGNATURES = {
     "pf_pngd_inflate_par": [vp, cl, C.c_uint32, vp, ci, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp],
     # ground-truth depth files (gtread.hip)
     "pf_gt_convert": [vp, ci, ci, ci, ci, ci, cf, cf, vp, vp, vp],
+    # training-side augmentations (augment.hip); m, colour and a are host arrays
+    "pf_aug_image_u8_to_f32": [vp, ci, ci, C.POINTER(C.c_double), ci, ci, cf, cf, C.POINTER(C.c_double), vp, vp],
+    "pf_aug_planes_nearest": [vp, vp, ci, ci, C.POINTER(ci), ci, vp, vp, vp],
 }
 NON_STATUS = ("pf_last_error", "pf_version", "pf_percentile_workspace_bytes", "pf_conv_winograd_fused_supported", "pf_gemm_split3_route",
               "pf_gemm_f16x2_points_route", "pf_gemm_f16x2_points_route_ex", "pf_conv_winograd_f16x2_supported_ex",

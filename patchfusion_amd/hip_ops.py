@@ -1508,5 +1508,36 @@ class HipOps:
                                _stream()), "pf_gt_convert")
         return depth
 
+    # ---------------- training-side augmentations (augment.hip) ----------------
+    @staticmethod
+    def aug_image_u8_to_f32(img_u8, matrix, flip, colour, out):
+        """img_u8 uint8 [H,W,3] in the raw file's order (B, G, R) -> out float32 [3,H,W] (R, G, B): Pillow's bilinear rotation with
+        Image.rotate's `matrix` (six Python floats), the flip, / 255 and, when colour = (gamma, brightness, (cr, cg, cb)) is not None,
+        aug_color's arithmetic (include/pf_hip.h).  gamma and brightness are rounded to float32 on the way in, as numpy does."""
+        H, W = img_u8.shape[0], img_u8.shape[1]
+        assert img_u8.dtype == torch.uint8 and tuple(img_u8.shape) == (H, W, 3) and img_u8.is_contiguous()
+        assert out.dtype == torch.float32 and tuple(out.shape) == (3, H, W) and out.is_contiguous()
+        m = (C.c_double * 6)(*[float(v) for v in matrix])
+        gamma, brightness, colours = colour if colour is not None else (1.0, 1.0, (1.0, 1.0, 1.0))
+        col = (C.c_double * 3)(*[float(v) for v in colours])
+        check(_L.pf_aug_image_u8_to_f32(_p(img_u8), H, W, m, int(bool(flip)), int(colour is not None), float(gamma), float(brightness), col,
+                                        _p(out), _stream()), "pf_aug_image_u8_to_f32")
+        return out
+
+    @staticmethod
+    def aug_planes_nearest(srcs, fixed, flip, outs):
+        """one or two float32 [H,W] planes -> the same rotated by Pillow's nearest-neighbour fixed-point path (`fixed`: the six 16.16
+        integers of include/pf_hip.h) and flipped; 0 outside the source"""
+        assert len(srcs) == len(outs) and len(srcs) in (1, 2)
+        H, W = srcs[0].shape
+        for t in tuple(srcs) + tuple(outs):
+            assert t.dtype == torch.float32 and tuple(t.shape) == (H, W) and t.is_contiguous()
+        a = [int(v) for v in fixed]
+        if len(a) != 6 or any(abs(v) >= 2 ** 31 for v in a):
+            raise ValueError(f"aug_planes_nearest: six 16.16 integers inside int32 are expected, got {fixed!r}")
+        check(_L.pf_aug_planes_nearest(_p(srcs[0]), _p(srcs[1]) if len(srcs) == 2 else None, H, W, (C.c_int * 6)(*a), int(bool(flip)),
+                                       _p(outs[0]), _p(outs[1]) if len(outs) == 2 else None, _stream()), "pf_aug_planes_nearest")
+        return outs
+
 
 ops = HipOps()

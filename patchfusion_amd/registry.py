@@ -1,14 +1,15 @@
 """mmengine config surface: registers the MI355X ``PatchFusion`` under the same registry name the
 reference uses (`estimator/registry/registry.py:6-7`, `estimator/models/builder.py:6-7`) so that
 ``build_model(cfg.model)`` with ``type='PatchFusion'`` resolves to this implementation; ``ImageDataset``
-(`estimator/datasets/general_dataset.py:145`) goes into a ``DATASETS`` registry the same way (``build_dataset``).
+(`estimator/datasets/general_dataset.py:145`) and ``UnrealStereo4kDataset`` (`estimator/datasets/u4k_dataset.py:21`) go into a
+``DATASETS`` registry the same way (``build_dataset``).
 
 With mmengine installed (the reference environment) the class is registered into a child of
 ``mmengine.registry.MODELS``; without it (this image) a minimal registry with the same
 ``register_module()`` / ``build(cfg)`` behaviour is provided so configs can still be built.
 """
 from .baseline import BaselinePretrain
-from .datasets import ImageDataset
+from .datasets import ImageDataset, UnrealStereo4kDataset
 from .model import PatchFusion
 
 try:
@@ -52,7 +53,7 @@ class _NoLoss:
 
 
 for _reg, _name, _cls in ((MODELS, 'PatchFusion', PatchFusion), (MODELS, 'BaselinePretrain', BaselinePretrain),
-                          (DATASETS, 'ImageDataset', ImageDataset)):
+                          (DATASETS, 'ImageDataset', ImageDataset), (DATASETS, 'UnrealStereo4kDataset', UnrealStereo4kDataset)):
     try:
         _reg.register_module(name=_name, module=_cls, force=True)
     except TypeError:  # pragma: no cover
