@@ -797,6 +797,44 @@ int pf_aug_image_u8_to_f32(const unsigned char* img, int H, int W, const double*
                            const double* colour, float* out, void* stream);
 int pf_aug_planes_nearest(const float* src0, const float* src1, int H, int W, const int* a, int flip, float* dst0, float* dst1, void* stream);
 
+/* ---- backward of the metric-bins head and of the SILog loss (csrc/head_bwd.hip) ----
+ * All tensors float32, NHWC with a pixel stride (ld) like the forward's.  No entry point uses a float atomic: every sum has a fixed order, two
+ * calls on the same operands give the same bits.  Every call refuses (PF_ERR_ARG, before any launch) a null or misaligned pointer (4 bytes for
+ * float, 8 for double), a size below 1 and a pixel stride below the channel count.
+ *
+ * pf_conv1x1_wgrad: dw[N][K] = sum_p dy[p][n] x[p][k] and (db not null) db[N] = sum_p dy[p][n] over P pixels, on the float32 MFMA
+ *   (v_mfma_f32_16x16x4_f32).  P is split into blocks of rows_per_block pixels (0: the default, about 512 blocks and never fewer than 512
+ *   pixels each); every block writes a partial [N][K] tile and a partial [N] to the workspace, a second launch adds them in block order.
+ *   pf_conv1x1_wgrad_workspace_bytes gives the workspace size for the same (P, N, K, rows_per_block); N, K <= 4096, at most 65535 blocks.
+ * pf_resize_bilinear_bwd: the adjoint of the align_corners=True bilinear resize [B,H,W,C] -> [B,OH,OW,C]: dx[B,H,W,C] (+)= up^T(dy[B,OH,OW,C]),
+ *   a gather over the destination pixels whose footprint holds the source pixel, with the forward's own weights; accumulate != 0 adds to dx.
+ * pf_attractor_bwd: AttractorLayerUnnormed.  With c = up(b_prev) [B,h,w,n_bins], dx = A_i - c_j, s = 1 / n_attr (kind 'mean') or 1 ('sum'),
+ *   f' = (1 - 300 dx^2) / (1 + 300 dx^2)^2 ('inv') or exp(-300 dx^2) (1 - 600 dx^2) ('exp') and g = d_b_new:
+ *   dA[B,h,w,i] = s sum_j g_j f'(dx),  d_b_c[B,h,w,j] = g_j (1 - s sum_i f'(dx)); the gradient of b_prev is pf_resize_bilinear_bwd of d_b_c.
+ *   n_bins <= 256.
+ * pf_logbinom_depth_bwd: pt [B,h,w,>=4] (after softplus), centers [B,hc,wc,n_bins], d_depth [B,h,w] -> d_pt [B,h,w,4] (stride d_pt_ld) and
+ *   d_centers_up [B,h,w,n_bins] = probs * d_depth (its resize adjoint is the gradient of centers).  The softmax is recomputed; the two
+ *   clamp(., 1e-4, 1) pass no gradient where they bind.  2 <= n_bins <= 256.  logc (device, n_bins floats, or null): log C(n_bins - 1, k) in the
+ *   Stirling form of dist_layers.py:29-45 as the reference's float32 tensor arithmetic gives it.  These are constants of the model; at a
+ *   temperature t a last-bit difference in one of them (1.5e-5 at values near 200) moves that bin's probability by 1.5e-5 / t, so a caller who
+ *   wants the reference's gradient hands in the reference's constants.  Null: the same expression evaluated in the kernel.
+ * pf_act_bwd: dy[p][c] *= act'; PF_ACT_RELU and PF_ACT_SOFTPLUS (1 - exp(-y)) take the layer's OUTPUT as ref, PF_ACT_GELU (exact erf form) the
+ *   PRE-ACTIVATION.
+ * pf_silog_loss_bwd: d_pred[n] = d_loss * dL/dpred from the three sums pf_silog_loss left in ws3 (count, sum g, sum g^2; unbiased variance);
+ *   all zeros when at most one pixel is valid (and where the loss is exactly zero, whose derivative does not exist). */
+int pf_conv1x1_wgrad_workspace_bytes(long P, int N, int K, int rows_per_block, long* bytes);
+int pf_conv1x1_wgrad(const float* dy, int dy_ld, const float* x, int x_ld, long P, int N, int K, float* dw, float* db, void* workspace,
+                     long workspace_bytes, int rows_per_block, void* stream);
+int pf_resize_bilinear_bwd(const float* dy, int dy_ld, int B, int OH, int OW, int C, float* dx, int dx_ld, int H, int W, int accumulate,
+                           void* stream);
+int pf_attractor_bwd(const float* A, int a_ld, int n_attr, int attractor_exp, int kind_sum, const float* b_prev, int hp, int wp,
+                     const float* d_b_new, float* dA, int da_ld, float* d_b_c, int B, int h, int w, int n_bins, void* stream);
+int pf_logbinom_depth_bwd(const float* pt, int pt_ld, const float* centers, int hc, int wc, const float* d_depth, float* d_pt, int d_pt_ld,
+                          float* d_centers_up, int B, int h, int w, int n_bins, float min_temp, float max_temp, const float* logc, void* stream);
+int pf_act_bwd(float* dy, int dy_ld, const float* ref, int ref_ld, long P, int C, int act, void* stream);
+int pf_silog_loss_bwd(const float* pred, const float* target, long n, float min_depth, float max_depth, float beta, const double* sums3,
+                      float d_loss, float* d_pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

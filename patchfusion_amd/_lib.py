@@ -187,6 +187,14 @@ SIGNATURES = {
     # training-side augmentations (augment.hip); m, colour and a are host arrays
     "pf_aug_image_u8_to_f32": [vp, ci, ci, C.POINTER(C.c_double), ci, ci, cf, cf, C.POINTER(C.c_double), vp, vp],
     "pf_aug_planes_nearest": [vp, vp, ci, ci, C.POINTER(ci), ci, vp, vp, vp],
+    # backward of the metric-bins head and of the SILog loss (head_bwd.hip)
+    "pf_conv1x1_wgrad_workspace_bytes": [cl, ci, ci, ci, C.POINTER(cl)],
+    "pf_conv1x1_wgrad": [vp, ci, vp, ci, cl, ci, ci, vp, vp, vp, cl, ci, vp],
+    "pf_resize_bilinear_bwd": [vp, ci, ci, ci, ci, ci, vp, ci, ci, ci, ci, vp],
+    "pf_attractor_bwd": [vp, ci, ci, ci, ci, vp, ci, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp],
+    "pf_logbinom_depth_bwd": [vp, ci, vp, ci, ci, vp, vp, ci, vp, ci, ci, ci, ci, cf, cf, vp, vp],
+    "pf_act_bwd": [vp, ci, vp, ci, cl, ci, ci, vp],
+    "pf_silog_loss_bwd": [vp, vp, cl, cf, cf, cf, vp, cf, vp, vp],
 }
 NON_STATUS = ("pf_last_error", "pf_version", "pf_percentile_workspace_bytes", "pf_conv_winograd_fused_supported", "pf_gemm_split3_route",
               "pf_gemm_f16x2_points_route", "pf_gemm_f16x2_points_route_ex", "pf_conv_winograd_f16x2_supported_ex",

@@ -47,7 +47,7 @@ class BaselinePretrain(PatchFusion):
         self.resizer = Resizer(self.patch_process_shape[1], self.patch_process_shape[0], 32 if self.branch_cfg.type == 'ZoeDepth' else 14)
         self.spec = OrderedDict()
         branch_spec(self.spec, self.prefix, self.branch_cfg)
-        _build_param_tree(self, self.spec)
+        _build_param_tree(self, self.spec, frozen_prefixes=())     # the pretraining model trains its branch (baseline_pretrain.py: no freeze)
         self.compute_dtype = _DTYPES[compute_dtype or "fp32"]
         self.shard_patches, self.overlap_coarse, self.overlap_batches, self.n_streams = False, False, False, 1
         self._ops, self._engine, self._coarse_state = ops, None, None
@@ -80,19 +80,46 @@ class BaselinePretrain(PatchFusion):
         return depth.unsqueeze(1)
 
     @torch.no_grad()
+    def train_forward(self, x, gt, head_grad=False):
+        """baseline_pretrain.py:347-363: the branch on the batch ``x`` [B,3,h,w] + SILogLoss against ``gt`` [B,1,H,W] ->
+        ``(loss_dict, {'rgb','depth_pred','depth_gt'})``, no autograd graph.  ``head_grad=True`` keeps the context of
+        :meth:`head_backward` (head-only fine-tuning over the frozen core, ZoeDepth's train_midas=False recipe; the head then takes its
+        unfused route, bit for bit the depth of PF_BINS_TAIL=0).  The backward of the core is not implemented."""
+        nets = self._ensure_engine()
+        net, ops = nets["branch"], self.ops
+        key = 'coarse_loss' if self.target == 'coarse' else 'fine_loss'
+        x = x.contiguous().float()
+        if head_grad:
+            from .engine import BranchNet
+            if not isinstance(net, BranchNet):
+                raise NotImplementedError("head backward: the head of an ExternalCoreBranchNet (type 'ZoeDepth', external MiDaS core) is not "
+                                          "implemented; only 'DA-ZoeDepth' branches")
+            net.head.check_trainable()                        # NotImplementedError before any launch
+            save = {}
+            depth, _ = net.forward(ops, x, head_save=save)
+        else:
+            save = None
+            depth, _ = net.forward(ops, x)
+        depth = depth.unsqueeze(1)
+        loss_dict = {key: self._sigloss(depth, gt, self.sigloss_cfg, save=save)}
+        loss_dict['total_loss'] = loss_dict[key]
+        if save is not None:
+            self._keep_head_context(save)
+        return loss_dict, {'rgb': x, 'depth_pred': depth, 'depth_gt': gt}
+
+    def _head_target(self):
+        return self._ensure_engine()["branch"].head, self.prefix
+
+    @torch.no_grad()
     def forward(self, mode, image_lr, image_hr, depth_gt=None, crop_depths=None, crops_image_hr=None, bboxs=None,
                 tile_cfg=None, cai_mode='m1', process_num=4, **kwargs):
         nets = self._ensure_engine()
         ops, dev = self.ops, self._device
         if mode == 'train':
-            # baseline_pretrain.py:347-363: the branch on the batch + SILogLoss.  FORWARD VALUE ONLY (no backward kernels), like
-            # PatchFusion.train_forward.
-            x, gt, key = (image_lr, depth_gt, 'coarse_loss') if self.target == 'coarse' else (crops_image_hr, crop_depths, 'fine_loss')
-            depth, _ = nets["branch"].forward(ops, x.contiguous().float())
-            depth = depth.unsqueeze(1)
-            loss_dict = {key: self._sigloss(depth, gt, self.sigloss_cfg)}
-            loss_dict['total_loss'] = loss_dict[key]
-            return loss_dict, {'rgb': image_lr, 'depth_pred': depth, 'depth_gt': gt}
+            x, gt = (image_lr, depth_gt) if self.target == 'coarse' else (crops_image_hr, crop_depths)
+            loss_dict, out = self.train_forward(x, gt)
+            out['rgb'] = image_lr
+            return loss_dict, out
         if self.target == 'coarse':
             depth = self.infer_forward(image_lr)
             return depth, {'rgb': image_lr, 'depth_pred': depth, 'depth_gt': depth_gt}

@@ -71,6 +71,13 @@ def _g(sd, name, device):
     return sd[name].detach().to(device=device, dtype=F32).contiguous()
 
 
+def _copy_pack(dst, src):
+    """overwrite the tensors of a packed layer (packing.PackedConv / BinsTail) with those of a fresh pack of the same shapes"""
+    for k, v in vars(src).items():
+        if isinstance(v, torch.Tensor):
+            getattr(dst, k).copy_(v)
+
+
 class BinsHead:
     """seed regressor/projector, 4 x (projector, attractor), conditional log-binomial, expectation."""
 
@@ -97,6 +104,11 @@ class BinsHead:
         self.emb = int(bcfg["bin_embedding_dim"])
         self.min_temp, self.max_temp = float(bcfg["min_temp"]), float(bcfg["max_temp"])
         self.with_rel = with_rel
+        self.prefix = prefix
+        self._pack(sd)
+
+    def _pack(self, sd):
+        prefix, dtype, device, with_rel = self.prefix, self.dtype, self.device, self.with_rel
 
         def pc(name, **kw):
             return pk.pack_conv(sd[prefix + name + ".weight"], sd[prefix + name + ".bias"], dtype=dtype, **kw).to(device)
@@ -111,7 +123,7 @@ class BinsHead:
             cmap, ctot = [(0, 32, 0), (32, 1, 32 + self.emb), (33, self.emb, 32)], 32 + self.emb + 8
         else:  # fusion head: rel_cond is all zeros (patchfusion.py:300) -> its column drops out exactly
             cmap, ctot = [(0, 32, 0), (33, self.emb, 32)], 32 + self.emb
-        self.clb_channels = ctot
+        self.clb_channels, self.clb_map = ctot, cmap
         self.mlp0 = pc("conditional_log_binomial.mlp.0", cin_map=cmap, cin_total=ctot)
         self.mlp2 = pc("conditional_log_binomial.mlp.2")
         # float32: resize-into-CLB + mlp.0 + mlp.2 + log-binomial as ONE kernel (pf_bins_tail) when the head has the shipped shape
@@ -120,19 +132,60 @@ class BinsHead:
             self.tail = pk.bins_tail_weights(self.mlp0, self.mlp2, self.emb)
             if self.tail is not None:
                 self.tail = self.tail.to(device)
+        self._bwd = None                                            # transposed packs of the backward, built on its first use
+
+    def refresh(self, sd):
+        """repack the head's 22 layers (and the fused tail's weights) from updated parameters, e.g. after optimizer.step(); the rest of the
+        engine is untouched.  ``sd``: a state dict with this head's keys under its prefix."""
+        new = object.__new__(BinsHead)
+        new.__dict__.update(self.__dict__)
+        new._pack(sd)                                               # fresh packs on `new`; this head's own are overwritten IN PLACE below, so
+        for a, b in zip(self._packs(), new._packs()):               # cached conv plans (hip_ops keys them by the pack object) stay valid
+            _copy_pack(a, b)
+        if self._bwd is not None:
+            for k, (_, _, t0, t2) in self._bwd.items():
+                _copy_pack(t0, new._bwd_packs()[k][2])
+                _copy_pack(t2, new._bwd_packs()[k][3])
+
+    def _packs(self):
+        flat = [self.sbr0, self.sbr2, self.sp0, self.sp2] + [p for pair in self.proj + self.attr for p in pair] + [self.mlp0, self.mlp2]
+        return flat + ([self.tail] if self.tail is not None else [])
+
+    @staticmethod
+    def param_names():
+        """the head's 44 checkpoint tensors, below its prefix"""
+        mlps = ["seed_bin_regressor", "seed_projector"] + [f"{k}.{i}" for k in ("projectors", "attractors") for i in range(4)]
+        layers = [f"{m}._net.{j}" for m in mlps for j in (0, 2)] + [f"conditional_log_binomial.mlp.{j}" for j in (0, 2)]
+        return [f"{l}.{t}" for l in layers for t in ("weight", "bias")]
+
+    def check_trainable(self):
+        """what :meth:`backward` does not cover, refused before any launch"""
+        if self.seed_bounded or self.attr_bounded:
+            raise NotImplementedError("head backward: bin_centers_type 'normed' / 'hybrid1' / 'hybrid2' (bounded centres: the backward would go "
+                                      "through a sort) is not implemented; only 'softplus'")
+        if self.dtype != F32:
+            raise NotImplementedError("head backward: compute_dtype='bf16' is not implemented; build the model with compute_dtype='fp32'")
 
     def new_clb_buffer(self, ops, B, H, W):
         return ops.empty((B, H, W, self.clb_channels), self.dtype, self.device)
 
-    def run(self, ops, x0, x_blocks, clb, taps=None):
+    def run(self, ops, x0, x_blocks, clb, taps=None, save=None):
         """x0 [B,h0,w0,C]; x_blocks 4 maps low->high; clb: buffer whose [..., :32] already holds `last`
-        (and [..., 160:168] the relative depth when with_rel).  Returns depth f32 [B,H,W]."""
+        (and [..., 160:168] the relative depth when with_rel).  Returns depth f32 [B,H,W].
+        ``save``: a dict that receives what :meth:`backward` needs (every layer's input, the attractor points A, each low-resolution b_prev,
+        pt and the last centres).  With it the head takes the unfused route -- pf_bins_tail keeps no pt -- so its depth is bit for bit that
+        of PF_BINS_TAIL=0; without it nothing changes."""
         dt, dev = self.dtype, self.device
+        if save is not None:
+            self.check_trainable()
+            save.update(mlps={}, layers=[])
         B, h0, w0, _ = x0.shape
         t = ops.empty((B, h0, w0, self.sbr0.cout), dt, dev)
         ops.conv(x0, self.sbr0, t, act="relu")
         b_prev = ops.empty((B, h0, w0, self.n_bins), F32, dev)
         ops.conv(t, self.sbr2, b_prev, act="relu" if self.seed_bounded else "softplus")
+        if save is not None:
+            save["mlps"]["seed_bin_regressor"] = (x0, t, b_prev)
         if self.seed_bounded or self.attr_bounded:                  # localbins_layers.py:52-68, zoedepth_v1.py:178-182
             b_prev = ops.seed_bin_centers(b_prev, ops.empty((B, h0, w0, self.n_bins), F32, dev), self.lo, self.hi,
                                           bounded=self.seed_bounded, normalize=self.attr_bounded)
@@ -140,6 +193,8 @@ class BinsHead:
         ops.conv(x0, self.sp0, t, act="relu")
         prev_emb = ops.empty((B, h0, w0, self.emb), dt, dev)
         ops.conv(t, self.sp2, prev_emb)
+        if save is not None:
+            save["mlps"]["seed_projector"] = (x0, t, prev_emb)
         emb = prev_emb
         for i, xb in enumerate(x_blocks):
             _, h, w, _ = xb.shape
@@ -148,6 +203,8 @@ class BinsHead:
             ops.conv(xb, p0, t, act="relu")
             emb = ops.empty((B, h, w, self.emb), dt, dev)
             ops.conv(t, p2, emb)
+            if save is not None:
+                save["mlps"][f"projectors.{i}"] = (xb, t, emb)
             xs = ops.empty((B, h, w, self.emb), dt, dev)
             ops.resize(prev_emb, xs, add=emb)                       # x = emb + up(prev_emb)
             a0, a2 = self.attr[i]
@@ -160,11 +217,14 @@ class BinsHead:
                 ops.attractor(A, self.n_attr[i], b_prev, b_new, a_stride=2, a_eps=1e-3, attractor_type=self.attr_type, kind=self.attr_kind)
             else:
                 ops.attractor(A, self.n_attr[i], b_prev, b_new, attractor_type=self.attr_type, kind=self.attr_kind)
+            if save is not None:
+                save["mlps"][f"attractors.{i}"] = (xs, t, A)
+                save["layers"].append((A, b_prev, tuple(prev_emb.shape[1:3])))
             b_prev, prev_emb = b_new, emb
             if taps is not None:
                 taps[f"bins_centers{i}"] = b_new
         _, H, W, _ = clb.shape
-        if self.tail is not None and emb.is_contiguous():
+        if self.tail is not None and emb.is_contiguous() and save is None:
             if self.attr_bounded:
                 b_prev = ops.bounded_bin_centers(b_prev, ops.empty(tuple(b_prev.shape), F32, dev), self.lo, self.hi)
             depth = ops.empty((B, H, W), F32, dev)
@@ -179,7 +239,111 @@ class BinsHead:
         if self.attr_bounded:                                       # attractor.py:132-135: the last layer's scaled, sorted, clipped centres
             b_prev = ops.bounded_bin_centers(b_prev, ops.empty(tuple(b_prev.shape), F32, dev), self.lo, self.hi)
         ops.logbinom_depth(pt, b_prev, depth, self.min_temp, self.max_temp)
+        if save is not None:
+            save.update(clb=clb, t=t, pt=pt, centers=b_prev, emb_hw=tuple(emb.shape[1:3]))
         return depth
+
+    # ---- backward (csrc/head_bwd.hip; float32, 'softplus' centres) ----
+    def _bwd_packs(self):
+        """W^T of every layer, packed like a forward weight: the data gradient dX = dY W is the forward 1x1 kernel on it.  Taken from the
+        forward pack, so mlp.0's is in the CLB buffer's channel order.  Input channels (= the layer's outputs) are padded to 8 with zero
+        weights; the gradient buffers are padded to match and zero there."""
+        if self._bwd is None:
+            def tr(pc):
+                w = pc.w[:pc.cout_real, :pc.cin].float().t().contiguous()            # [cin_total, N]
+                return pk.pack_conv(w, None, dtype=F32).to(self.device)
+            named = {"seed_bin_regressor": (self.sbr0, self.sbr2), "seed_projector": (self.sp0, self.sp2)}
+            for i in range(4):
+                named[f"projectors.{i}"], named[f"attractors.{i}"] = self.proj[i], self.attr[i]
+            self._bwd = {k: (p0, p2, tr(p0), tr(p2)) for k, (p0, p2) in named.items()}
+            self._bwd["clb"] = (self.mlp0, self.mlp2, tr(self.mlp0), tr(self.mlp2))
+        return self._bwd
+
+    def _wgrad(self, ops, name, pc, dy, x, grads, cmap=None):
+        """grads[name.weight / .bias] of one 1x1 layer: dy [..., N] (a view of the padded gradient buffer), x the layer's input buffer"""
+        N, dev = pc.cout_real, self.device
+        dw, db = ops.empty((N, x.shape[-1]), F32, dev), ops.empty((N,), F32, dev)
+        ops.conv1x1_wgrad(dy, x, dw, db)
+        if cmap is not None:                                        # mlp.0: from the CLB buffer's channel order back to the checkpoint's
+            full = ops.zeros((N, 33 + self.emb), F32, dev)          # (the fusion head's rel column reads zeros: zero gradient)
+            for s0, n, d0 in cmap:
+                full[:, s0:s0 + n] = dw[:, d0:d0 + n]
+            dw = full
+        grads[name + ".weight"], grads[name + ".bias"] = dw.view(N, dw.shape[1], 1, 1), db
+
+    def _mlp_bwd(self, ops, key, saved, dy_buf, grads, act_out=None, res=None):
+        """backward of Conv1x1 - ReLU - Conv1x1 [- Softplus].  dy_buf: the gradient of the output, channels padded to 8 (zeros in the padding).
+        -> the gradient of the input (+ res)"""
+        p0, p2, p0t, p2t = self._bwd_packs()[key]
+        x, h, y = saved[key]
+        dy = dy_buf[..., :p2.cout_real]
+        if act_out is not None:
+            ops.act_bwd(dy, y, act_out)
+        self._wgrad(ops, key + "._net.2", p2, dy, h, grads)
+        dh = ops.empty(tuple(h.shape), F32, self.device)
+        ops.conv(dy_buf, p2t, dh)
+        ops.act_bwd(dh, h, "relu")
+        self._wgrad(ops, key + "._net.0", p0, dh, x, grads)
+        dx = ops.empty(tuple(x.shape), F32, self.device)
+        ops.conv(dh, p0t, dx, res=res)
+        return dx
+
+    def backward(self, ops, ctx, d_depth):
+        """ctx: the dict :meth:`run` filled through ``save``; d_depth f32 [B,H,W] (contiguous).  -> (param_grads, input_grads):
+        param_grads keyed by the checkpoint names below this head's prefix ('seed_bin_regressor._net.0.weight', ...: 22 layers, 44 tensors),
+        input_grads = {'x0', 'x_blocks' (list, low -> high), 'last'[, 'rel']} (NHWC; 'last' and 'rel' are channel slices of one buffer).
+        Fixed summation orders throughout: two calls on one context give identical bits."""
+        self.check_trainable()
+        dev, sv, grads = self.device, ctx["mlps"], {}
+        clb, pt, centers = ctx["clb"], ctx["pt"], ctx["centers"]
+        B, H, W, _ = clb.shape
+        mlp0, mlp2, mlp0t, mlp2t = self._bwd_packs()["clb"]
+        # log-binomial expectation -> pt and the last centres
+        d_pt = ops.zeros((B, H, W, 8), F32, dev)
+        d_cup = ops.empty((B, H, W, self.n_bins), F32, dev)
+        ops.logbinom_depth_bwd(pt, centers, d_depth, d_pt[..., :4], d_cup, self.min_temp, self.max_temp)
+        g = ops.empty(tuple(centers.shape), F32, dev)
+        ops.resize_bwd(d_cup, g)
+        d_cup = None
+        # mlp.2 (softplus), mlp.0 (gelu: the pre-activation is recomputed, the forward keeps only its output)
+        ops.act_bwd(d_pt[..., :4], pt, "softplus")
+        self._wgrad(ops, "conditional_log_binomial.mlp.2", mlp2, d_pt[..., :4], ctx["t"], grads)
+        d_t = ops.empty(tuple(ctx["t"].shape), F32, dev)
+        ops.conv(d_pt, mlp2t, d_t)
+        t_pre = ops.empty(tuple(ctx["t"].shape), F32, dev)
+        ops.conv(clb, mlp0, t_pre)
+        ops.act_bwd(d_t, t_pre, "gelu")
+        t_pre = None
+        self._wgrad(ops, "conditional_log_binomial.mlp.0", mlp0, d_t, clb, grads, cmap=self.clb_map)
+        d_clb = ops.empty(tuple(clb.shape), F32, dev)
+        ops.conv(d_t, mlp0t, d_clb)
+        inp = {"last": d_clb[..., :32]}
+        if self.with_rel:
+            inp["rel"] = d_clb[..., 32 + self.emb:33 + self.emb]
+        d_emb_up = d_clb[..., 32:32 + self.emb]                     # gradient of the up-sampled embedding
+        # attractor layers, last to first.  total gradient of emb_i = d_xs_i + up^T(what reads emb_i later): the later reader is the tail
+        # (i = 3) or layer i + 1's x = emb_{i+1} + up(emb_i)
+        later, d_blocks = d_emb_up, [None] * len(ctx["layers"])
+        for i in reversed(range(len(ctx["layers"]))):
+            A, b_prev, prev_hw = ctx["layers"][i]
+            n_attr = self.n_attr[i]
+            dA = ops.zeros(tuple(A.shape[:3]) + ((n_attr + 7) // 8 * 8,), F32, dev)
+            d_bc = ops.empty(tuple(A.shape[:3]) + (self.n_bins,), F32, dev)
+            ops.attractor_bwd(A, n_attr, b_prev, g, dA[..., :n_attr], d_bc, attractor_type=self.attr_type, kind=self.attr_kind)
+            g = ops.empty(tuple(b_prev.shape), F32, dev)
+            ops.resize_bwd(d_bc, g)
+            d_xs = self._mlp_bwd(ops, f"attractors.{i}", sv, dA, grads, act_out="softplus")
+            d_emb = ops.empty(tuple(d_xs.shape), F32, dev)
+            ops.copy_channels(d_xs, d_emb)
+            ops.resize_bwd(later, d_emb, accumulate=True)
+            d_blocks[i] = self._mlp_bwd(ops, f"projectors.{i}", sv, d_emb, grads)
+            later = d_xs
+        d_prev = ops.empty((B,) + tuple(ctx["layers"][0][2]) + (self.emb,), F32, dev)
+        ops.resize_bwd(later, d_prev)
+        dx0 = self._mlp_bwd(ops, "seed_projector", sv, d_prev, grads)
+        inp["x0"] = self._mlp_bwd(ops, "seed_bin_regressor", sv, g, grads, act_out="softplus", res=dx0)
+        inp["x_blocks"] = d_blocks
+        return grads, inp
 
 
 class BranchNet:
@@ -375,10 +539,11 @@ class BranchNet:
                 feats.append(f)
         return feats
 
-    def forward(self, ops, img, taps=None, vit_feats=None):
+    def forward(self, ops, img, taps=None, vit_feats=None, head_save=None):
         """img [B,3,H,W] float32 in [0,1] -> (depth f32 [B,H,W], feats low->high
         [x_d0, r4, r3, r2, r1, out_conv(32)]).  ``vit_feats``: the four encoder outputs of these B images when the caller has already
-        run :meth:`vit` on a larger batch (all tiles of an image in one launch per layer: fewer, better-filled GEMM launches)."""
+        run :meth:`vit` on a larger batch (all tiles of an image in one launch per layer: fewer, better-filled GEMM launches).
+        ``head_save``: BinsHead.run's ``save``."""
         dt, dev = self.dtype, self.device
         B = img.shape[0]
         th, tw, C = self.th, self.tw, self.C
@@ -424,7 +589,7 @@ class BranchNet:
         ops.conv(rn[3], self.conv2, x_d0)
         if taps is not None:
             taps.update(dpt_layer1_rn=rn[0], dpt_layer4_rn=rn[3], rel_depth=clb[..., 32 + self.head.emb:33 + self.head.emb])
-        depth = self.head.run(ops, x_d0, [r4, r3, r2, r1], clb, taps)
+        depth = self.head.run(ops, x_d0, [r4, r3, r2, r1], clb, taps, save=head_save)
         return depth, [x_d0, r4, r3, r2, r1, out_conv]
 
 
@@ -587,7 +752,7 @@ class FusionNet:
         self.head = BinsHead(sd, "", self.C, cfg["coarse_branch"], dtype, device, with_rel=False,
                              min_depth=cfg["min_depth"], max_depth=cfg["max_depth"])
 
-    def forward(self, ops, crops, rois, fine_depth, fine_feats, coarse_depth, coarse_feats, g2l, taps=None):
+    def forward(self, ops, crops, rois, fine_depth, fine_feats, coarse_depth, coarse_feats, g2l, taps=None, head_save=None):
         """crops [B,3,H,W] f32; rois f32 [B,5] (batch index 0, box in process coordinates);
         fine_depth f32 [B,H,W]; coarse_depth f32 [1,1,H,W]; returns depth f32 [B,H,W]."""
         dt, dev = self.dtype, self.device
@@ -682,4 +847,4 @@ class FusionNet:
             fused.append(temp)
             if taps is not None:
                 taps[f"gf_out{i}"] = temp
-        return self.head.run(ops, fused[0], fused[1:5], clb, taps)
+        return self.head.run(ops, fused[0], fused[1:5], clb, taps, save=head_save)

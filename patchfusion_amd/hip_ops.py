@@ -68,6 +68,21 @@ def _ld(t):
     return ld
 
 
+_LOGC = {}
+
+
+def _logbinom_logc(n_bins, device):
+    """log C(n_bins - 1, k), k = 0 .. n_bins - 1, as the reference computes it (dist_layers.py:29-45: float32 tensor arithmetic in torch, Stirling
+    form with eps = 1e-7), once per (n_bins, device): constants of the model, handed to pf_logbinom_depth_bwd (include/pf_hip.h says why)"""
+    key = (int(n_bins), device)
+    if key not in _LOGC:
+        eps = 1e-7
+        k = torch.arange(n_bins, dtype=torch.float32) + eps
+        n = torch.full((1,), float(n_bins - 1)) + eps
+        _LOGC[key] = (n * torch.log(n) - k * torch.log(k) - (n - k) * torch.log(n - k + eps)).to(device)
+    return _LOGC[key]
+
+
 _ENV = {}
 
 
@@ -1068,6 +1083,85 @@ class HipOps:
         assert emb.is_contiguous() and centers.is_contiguous() and depth.is_contiguous() and clb.stride(3) == 1
         check(_L.pf_bins_tail(_p(clb), _ld(clb), tw.rel_off, _p(emb), he, we, _p(tw.w0f), _p(tw.b0), _p(tw.w2), _p(tw.b2), _p(centers), hc, wc,
                               _p(depth), B, H, W, tw.nq, float(min_temp), float(max_temp), _stream()), "pf_bins_tail")
+
+    # ---------------- backward of the metric-bins head (csrc/head_bwd.hip; float32 only, fixed summation orders) ----------------
+    @staticmethod
+    def conv1x1_wgrad(dy, x, dw, db=None, rows_per_block=0):
+        """dy [..., >=N] and x [..., >=K] float32 NHWC views over the same pixels (channel slices fine) -> dw [N, K] = sum_p dy x, db [N] = sum_p dy
+        (include/pf_hip.h: pf_conv1x1_wgrad).  rows_per_block: pixels per partial tile, 0 = the library's default."""
+        N, K = dw.shape
+        dy4, x4 = _as4(dy), _as4(x)
+        P = dy4.numel() // dy4.shape[-1]
+        assert dy.dtype == x.dtype == dw.dtype == torch.float32 and dw.is_contiguous() and dy4.shape[:3] == x4.shape[:3]
+        assert dy4.shape[-1] >= N and x4.shape[-1] >= K and (db is None or (db.dtype == torch.float32 and db.is_contiguous() and db.numel() == N))
+        need = C.c_long(0)
+        check(_L.pf_conv1x1_wgrad_workspace_bytes(P, N, K, int(rows_per_block), C.byref(need)), "pf_conv1x1_wgrad_workspace_bytes")
+        ws = torch.empty(need.value // 4, dtype=torch.float32, device=dw.device)
+        check(_L.pf_conv1x1_wgrad(_p(dy4), _ld(dy4), _p(x4), _ld(x4), P, N, K, _p(dw), _p(db), _p(ws), need.value, int(rows_per_block), _stream()),
+              "pf_conv1x1_wgrad")
+        return dw, db
+
+    @staticmethod
+    def resize_bwd(dy, dx, accumulate=False):
+        """adjoint of the align_corners=True bilinear resize: dy [B,OH,OW,C] -> dx [B,H,W,C] (+= with accumulate); float32, channel slices fine"""
+        B, OH, OW, Cc = dy.shape
+        Bx, H, W, Cx = dx.shape
+        assert dy.dtype == dx.dtype == torch.float32 and B == Bx and Cc == Cx
+        check(_L.pf_resize_bilinear_bwd(_p(dy), _ld(dy), B, OH, OW, Cc, _p(dx), _ld(dx), H, W, int(bool(accumulate)), _stream()),
+              "pf_resize_bilinear_bwd")
+        return dx
+
+    @staticmethod
+    def attractor_bwd(A, n_attr, b_prev, d_b_new, dA, d_b_c, attractor_type="inv", kind="mean"):
+        """A [B,h,w,>=n_attr], b_prev [B,hp,wp,n_bins], d_b_new [B,h,w,n_bins] -> dA [B,h,w,>=n_attr], d_b_c [B,h,w,n_bins] (pf_attractor_bwd)"""
+        B, h, w, nb = d_b_new.shape
+        _, hp, wp, _ = b_prev.shape
+        assert A.dtype == b_prev.dtype == d_b_new.dtype == dA.dtype == d_b_c.dtype == torch.float32 and kind in ("mean", "sum")
+        assert b_prev.is_contiguous() and d_b_new.is_contiguous() and d_b_c.is_contiguous() and d_b_c.shape == d_b_new.shape
+        assert A.shape[:3] == dA.shape[:3] == (B, h, w) and A.shape[-1] >= n_attr and dA.shape[-1] >= n_attr and b_prev.shape[-1] == nb
+        check(_L.pf_attractor_bwd(_p(A), _ld(A), int(n_attr), int(attractor_type == "exp"), int(kind == "sum"), _p(b_prev), hp, wp, _p(d_b_new),
+                                  _p(dA), _ld(dA), _p(d_b_c), B, h, w, nb, _stream()), "pf_attractor_bwd")
+        return dA, d_b_c
+
+    @staticmethod
+    def logbinom_depth_bwd(pt, centers, d_depth, d_pt, d_centers_up, min_temp, max_temp):
+        """pt [B,h,w,>=4] (softplus applied), centers [B,hc,wc,n_bins], d_depth [B,h,w] -> d_pt [B,h,w,>=4], d_centers_up [B,h,w,n_bins]"""
+        B, h, w = d_depth.shape
+        _, hc, wc, nb = centers.shape
+        assert pt.dtype == centers.dtype == d_depth.dtype == d_pt.dtype == d_centers_up.dtype == torch.float32
+        assert centers.is_contiguous() and d_depth.is_contiguous() and d_centers_up.is_contiguous() and tuple(d_centers_up.shape) == (B, h, w, nb)
+        assert pt.shape[:3] == d_pt.shape[:3] == (B, h, w)
+        check(_L.pf_logbinom_depth_bwd(_p(pt), _ld(pt), _p(centers), hc, wc, _p(d_depth), _p(d_pt), _ld(d_pt), _p(d_centers_up), B, h, w, nb,
+                                       float(min_temp), float(max_temp), _p(_logbinom_logc(nb, pt.device)), _stream()), "pf_logbinom_depth_bwd")
+        return d_pt, d_centers_up
+
+    @staticmethod
+    def act_bwd(dy, ref, act):
+        """in place dy *= act'; ref = the layer's output for 'relu' / 'softplus', its pre-activation for 'gelu'; NHWC float32 views over the same pixels"""
+        dy4, r4 = _as4(dy), _as4(ref)
+        Cc = dy4.shape[-1]
+        assert dy.dtype == ref.dtype == torch.float32 and dy4.shape[:3] == r4.shape[:3] and r4.shape[-1] >= Cc and act in ("relu", "gelu", "softplus")
+        check(_L.pf_act_bwd(_p(dy4), _ld(dy4), _p(r4), _ld(r4), dy4.numel() // Cc, Cc, ACT[act], _stream()), "pf_act_bwd")
+        return dy
+
+    @staticmethod
+    def silog_loss_saved(pred, target, min_depth, max_depth, beta=0.15):
+        """silog_loss that also returns the three float64 sums (count, sum g, sum g^2) its backward needs -> (loss, sums)"""
+        assert pred.dtype == target.dtype == torch.float32 and pred.shape == target.shape and pred.is_contiguous() and target.is_contiguous()
+        ws = torch.empty(3, dtype=torch.float64, device=pred.device)
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        check(_L.pf_silog_loss(_p(pred), _p(target), pred.numel(), float(min_depth), float(max_depth), float(beta), _p(ws), _p(loss),
+                               _stream()), "pf_silog_loss")
+        return loss, ws
+
+    @staticmethod
+    def silog_loss_bwd(pred, target, sums, d_pred, min_depth, max_depth, beta=0.15, d_loss=1.0):
+        """d_pred = d_loss * dL/dpred of silog_loss, from the sums silog_loss_saved returned; pred, target, d_pred float32 of equal shape"""
+        assert pred.dtype == target.dtype == d_pred.dtype == torch.float32 and pred.shape == target.shape == d_pred.shape
+        assert pred.is_contiguous() and target.is_contiguous() and d_pred.is_contiguous() and sums.dtype == torch.float64 and sums.numel() == 3
+        check(_L.pf_silog_loss_bwd(_p(pred), _p(target), pred.numel(), float(min_depth), float(max_depth), float(beta), _p(sums), float(d_loss),
+                                   _p(d_pred), _stream()), "pf_silog_loss_bwd")
+        return d_pred
 
     # ---------------- stitching ----------------
     @staticmethod

@@ -84,9 +84,10 @@ class Resizer:
         return F.interpolate(x, (nh, nw), mode='bilinear', align_corners=True)
 
 
-def _build_param_tree(root, spec):
+def _build_param_tree(root, spec, frozen_prefixes=("coarse_branch.", "fine_branch.")):
     """Register every checkpoint tensor under its dotted name so state_dict()/load_state_dict()/.to()
-    behave exactly like the reference's module tree (containers only, no forward code)."""
+    behave exactly like the reference's module tree (containers only, no forward code).  ``frozen_prefixes``: parameters built with
+    requires_grad=False -- the two branches inside PatchFusion; BaselinePretrain, which trains its branch, passes none."""
     for name, e in spec.items():
         parts = name.split('.')
         mod = root
@@ -98,7 +99,7 @@ def _build_param_tree(root, spec):
         if e.dtype.is_floating_point and e.kind not in ("bn_mean", "bn_var", "k_minus_1"):
             # like the reference: branch parameters frozen (patchfusion.py:111-115), fusion-side parameters trainable
             # (so that DistributedDataParallel(model) in tools/test.py:221 accepts the module)
-            frozen = name.startswith(("coarse_branch.", "fine_branch."))
+            frozen = bool(frozen_prefixes) and name.startswith(tuple(frozen_prefixes))
             mod.register_parameter(leaf, nn.Parameter(torch.zeros(e.shape, dtype=e.dtype), requires_grad=not frozen))
         else:
             mod.register_buffer(leaf, torch.zeros(e.shape, dtype=e.dtype))
@@ -615,17 +616,24 @@ class PatchFusion(nn.Module, PyTorchModelHubMixin):
             avg = a2
         return avg
 
-    # ------------------------------------------------------------------ training-mode forward (forward VALUE only)
+    # ------------------------------------------------------------------ training-mode forward
     @torch.no_grad()
-    def train_forward(self, image_lr, crops_image_hr, crop_depths, bboxs):
+    def train_forward(self, image_lr, crops_image_hr, crop_depths, bboxs, head_grad=False):
         """``forward(mode='train')`` of the reference, patchfusion.py:372-399: B images, one random crop
         each -> coarse branch on ``image_lr`` [B,3,h,w], fine branch on ``crops_image_hr`` [B,3,h,w],
         ``coarse_postprocess_train`` (roi_align of image i's coarse maps with box i, :227-237), ``fusion_forward``, SILogLoss
         against ``crop_depths`` [B,1,h,w].  Returns ``(loss_dict, {'rgb','depth_pred','depth_gt'})`` like the reference.
-        FORWARD VALUE ONLY: the engine has no backward kernels, the returned tensors carry no autograd graph (use it for
-        validation loss / to check a training pipeline's data path; optimisation steps need the reference's PyTorch modules)."""
+        The returned tensors carry no autograd graph.  ``head_grad=True`` keeps what :meth:`head_backward` needs (the fusion head then
+        takes its unfused route: its depth is bit for bit that of PF_BINS_TAIL=0); the backward of everything below the head --
+        FusionNet, G2LNet, the branches -- is not implemented, their optimisation steps stay with the reference's PyTorch modules."""
         nets = self._ensure_engine()
         ops, dev = self.ops, self._device
+        save = None
+        if head_grad:
+            if crop_depths is None:
+                raise ValueError("train_forward(head_grad=True) needs crop_depths: the context is that of the loss")
+            nets["fusion"].head.check_trainable()             # NotImplementedError before any launch
+            save = {}
         B = image_lr.shape[0]
         assert crops_image_hr.shape[0] == B and bboxs.shape[0] == B
         H, W = self.tile_cfg['image_raw_shape']
@@ -638,22 +646,84 @@ class PatchFusion(nn.Module, PyTorchModelHubMixin):
         g2l = nets["g2l"].forward(ops, cfeats)            # per image here (batch B): the coarse maps differ per sample
         crops = crops_image_hr.contiguous().float()
         fdepth, ffeats = nets["fine"].forward(ops, crops)
-        d = nets["fusion"].forward(ops, crops, rois, fdepth, ffeats, cdepth.view(B, 1, *cdepth.shape[1:]), cfeats, g2l)
+        if save is None:
+            d = nets["fusion"].forward(ops, crops, rois, fdepth, ffeats, cdepth.view(B, 1, *cdepth.shape[1:]), cfeats, g2l)
+        else:
+            d = nets["fusion"].forward(ops, crops, rois, fdepth, ffeats, cdepth.view(B, 1, *cdepth.shape[1:]), cfeats, g2l, head_save=save)
         depth_prediction = d.unsqueeze(1)
         loss_dict = {}
         if crop_depths is not None:
-            loss_dict['sig_loss'] = self._sigloss(depth_prediction, crop_depths, self.config.get('sigloss'))
+            loss_dict['sig_loss'] = self._sigloss(depth_prediction, crop_depths, self.config.get('sigloss'), save=save)
             loss_dict['total_loss'] = loss_dict['sig_loss']
+        if save is not None:
+            self._keep_head_context(save)
         return loss_dict, {'rgb': crops_image_hr, 'depth_pred': depth_prediction, 'depth_gt': crop_depths}
 
-    def _sigloss(self, pred, target, sigloss_cfg=None):
+    def _sigloss(self, pred, target, sigloss_cfg=None, save=None):
         """SILogLoss.forward (losses.py:15-62) on the device: bilinear align_corners resize of the prediction when the grids differ
-        (:27-28), then the masked scale-invariant log loss (pf_silog_loss); beta from the loss config (default 0.15)."""
+        (:27-28), then the masked scale-invariant log loss (pf_silog_loss); beta from the loss config (default 0.15).
+        ``save``: a dict that receives what the loss's backward needs (head_backward)."""
         gt = target.to(device=self._device, dtype=torch.float32)
-        if tuple(gt.shape[-2:]) != tuple(pred.shape[-2:]):
+        pred_hw = tuple(pred.shape[-2:])
+        if tuple(gt.shape[-2:]) != pred_hw:
             pred = F.interpolate(pred, tuple(gt.shape[-2:]), mode='bilinear', align_corners=True)
         beta = float(sigloss_cfg.get('beta', 0.15)) if isinstance(sigloss_cfg, dict) else 0.15
-        return self.ops.silog_loss(pred.contiguous(), gt.contiguous(), self.min_depth, self.max_depth, beta)
+        if save is None:
+            return self.ops.silog_loss(pred.contiguous(), gt.contiguous(), self.min_depth, self.max_depth, beta)
+        pred, gt = pred.contiguous(), gt.contiguous()
+        loss, sums = self.ops.silog_loss_saved(pred, gt, self.min_depth, self.max_depth, beta)
+        save["loss"] = dict(pred=pred, gt=gt, sums=sums, beta=beta, pred_hw=pred_hw)
+        return loss
+
+    # ------------------------------------------------------------------ head training: backward of the metric-bins head and the loss
+    def _head_target(self):
+        """(the BinsHead that head_backward / refresh_head work on, its checkpoint prefix): the fusion head"""
+        return self._ensure_engine()["fusion"].head, ""
+
+    def _keep_head_context(self, save):
+        head, prefix = self._head_target()
+        params = {n: self.get_parameter(prefix + n) for n in head.param_names()}
+        self._head_ctx = dict(save=save, engine=self._engine, versions={n: p._version for n, p in params.items()})
+
+    @torch.no_grad()
+    def head_backward(self):
+        """Backward of the SILog loss and of the metric-bins head for the last ``train_forward(..., head_grad=True)``: accumulates into
+        ``.grad`` of the head's 22 weight / bias pairs, as ``loss.backward()`` would, and returns the gradients that reach the head's
+        inputs ``{'x0', 'x_blocks', 'last'[, 'rel']}`` (NHWC float32) for the stages below it.  Raises without a context, after the engine
+        was rebuilt, or when a head parameter changed since the forward (its ``_version`` differs).  Two calls on one context add the same
+        bits twice."""
+        ctx = getattr(self, "_head_ctx", None)
+        if ctx is None:
+            raise RuntimeError("head_backward(): no context -- call train_forward(..., head_grad=True) first")
+        if ctx["engine"] is not self._engine:
+            raise RuntimeError("head_backward(): the engine was rebuilt since the forward (load_state_dict / .to / set_compute_dtype); run the forward again")
+        head, prefix = self._head_target()
+        params = {n: self.get_parameter(prefix + n) for n in head.param_names()}
+        stale = [n for n, p in params.items() if p._version != ctx["versions"][n]]
+        if stale:
+            raise RuntimeError(f"head_backward(): {len(stale)} head parameters changed since the forward (first: {prefix + stale[0]}); "
+                               "the saved activations belong to the old weights -- run the forward again")
+        ops, dev, save = self.ops, self._device, ctx["save"]
+        L = save["loss"]
+        B, _, H, W = L["gt"].shape
+        d_pred = ops.empty(tuple(L["pred"].shape), torch.float32, dev)
+        ops.silog_loss_bwd(L["pred"], L["gt"], L["sums"], d_pred, self.min_depth, self.max_depth, L["beta"])
+        if L["pred_hw"] != (H, W):                            # the loss saw the up-sampled prediction: its adjoint takes the gradient down
+            d = ops.empty((B,) + L["pred_hw"] + (1,), torch.float32, dev)
+            ops.resize_bwd(d_pred.view(B, H, W, 1), d)
+            d_pred = d
+        grads, inputs = head.backward(ops, save, d_pred.view(B, *L["pred_hw"]))
+        for n, p in params.items():
+            g = grads[n].to(p.dtype)
+            p.grad = g.clone() if p.grad is None else p.grad.add_(g)
+        return inputs
+
+    def refresh_head(self):
+        """after ``optimizer.step()``: repack the head's layers (and the fused tail's weights) from the updated parameters; the rest of
+        the engine is untouched.  Drops the saved context."""
+        head, _ = self._head_target()
+        head.refresh(self.state_dict())
+        self._head_ctx = None
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
