@@ -1,5 +1,6 @@
 // ViT attention in split precision, version 2 (round 6): the kernel that replaces vit_attention_split3_kernel (csrc/vit.hip) on the float32 headline
-// path.  Same arithmetic, operand order and results (bit-identical: tests/op_checks.py vit_attention_split3_v2) -- softmax(q k^T / 8) v per head,
+// path.  Same arithmetic, operand order and results (bit-identical: tests/op_checks.py vit_attention_split3_v2 and, at the ragged and key-split shapes, tests/test_attention_grade_gpu.py, which
+// also holds every kernel of this file to float64 element by element) -- softmax(q k^T / 8) v per head,
 // head_dim 64 (dinov2/layers/attention.py:49-62), q / k / v and the output as three bf16 planes (x = h + m + l, csrc/gemm_split3.hip), both matrix
 // products as the six leading partial products on v_mfma_f32_16x16x32_bf16 with float32 accumulation, float32 online softmax on base-2 logits.
 //
@@ -372,7 +373,8 @@ __global__ __launch_bounds__(256, 2) void vit_attention_split3_rpb_kernel(const 
 //   Blocks past the sequence are fetched as clamped re-reads of row S - 1 (uniform vmcnt accounting) and never enter a softmax.
 //   Grid order: the 13-query tail blocks of every (image, head) come FIRST, so they run beside full blocks instead of alone at the end.
 // Arithmetic: the same six products, smallest first, per accumulator; the online softmax advances in 32-key blocks, so results agree with version 1 to
-// float32 rounding, not bit for bit (tests/op_checks.py vit_attention_split3_v2: error against float64 <= version 1's).
+// float32 rounding, not bit for bit (tests/op_checks.py vit_attention_split3_v2: error against float64 <= version 1's; per element, key-split tail
+// blocks of 1 and of 32 queries under both block orders included: tests/test_attention_grade_gpu.py).
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 #ifdef PF_ATTN_DBG
 // s_memtime timeline of the pipelined kernel (decomposition build only): per-phase cycle sums of wave 0 of three blocks, read back by pf_attn_dbg_timeline
