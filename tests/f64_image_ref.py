@@ -1,7 +1,7 @@
 """Float64 references and per-element magnitudes of the non-GEMM kernels (csrc/imageops.hip, csrc/swin.hip): bilinear / nearest resize, crop-resize,
 roi_align, maxpool2, the tile stitcher, the Swin (G2L) partition / window attention / reverse, and the attractor / log-binomial kernels of the
-metric-bins head.  Style and metric of tests/f64_ref.py; used by tests/test_image_grade_gpu.py, checked on the CPU by
-tests/test_f64_image_ref_cpu.py.  No GPU needed.
+metric-bins head, the fused metric-bins tail and the seed / bounded bin centres.  Style and metric of tests/f64_ref.py; used by
+tests/test_image_grade_gpu.py and tests/test_tail_grade_gpu.py, checked on the CPU by tests/test_f64_image_ref_cpu.py.  No GPU needed.
 
 Every function takes the operands the kernel sees (float32 tensors, or bf16 tensors read as their exact values; scalar arguments as the float32 the
 C ABI passes) and returns (ref, mag) in float64 for EVERY output element.  What the operation defines in float32 is evaluated in float32 here too:
@@ -317,7 +317,7 @@ def logbinom_logc(nb):
 def logbinom_depth_ref(pt, centers, h, w, min_temp, max_temp):
     """pt [B, h, w, >= 4] (p0, p1, t0, t1, softplus applied), centers [B, hc, wc, nb] -> (ref, mag) [B, h, w]:
     p = p0 / (p0 + p1), t = (max_temp - min_temp) t0 / (t0 + t1) + min_temp (each + 1e-4 first), softmax_k((log C(n, k) + k log p + (n - k) log(1 - p)) / t)
-    . up(centers).  mag = sum_k p_k |center_k|"""
+    . up(centers).  mag = sum_k p_k |center_k|.  A float64 pt is taken as it is (bins_tail_ref hands over the unrounded softplus outputs)"""
     e4 = float(f32(1e-4))
     q = _d(pt)[..., :4] + e4
     p = q[..., 0] / (q[..., 0] + q[..., 1])
@@ -332,6 +332,53 @@ def logbinom_depth_ref(pt, centers, h, w, min_temp, max_temp):
     pr = yk.softmax(-1)
     c, cm = bilinear_ref(centers, h, w)
     return (pr * c).sum(-1), (pr * cm).sum(-1)
+
+
+def bins_tail_ref(last, rel, emb, w0, b0, w2, b2, centers, H, W, min_temp, max_temp):
+    """the fused metric-bins tail (csrc/imageops.hip bins_tail_kernel) in float64 from its float32 operands: last [B, H, W, 32], rel [B, H, W, 8] or
+    None, emb [B, he, we, 128], w0 [80, ctot] over the channel order of the CLB buffer (last, embedding, rel), b0 [80], w2 [4, 80], b2 [4], centers
+    [B, hc, wc, 64] -> (depth, mag) [B, H, W].  x = cat[last, up(emb), rel] (bilinear_ref: the float32 source coordinate, float64 blend), W0 x + b0,
+    erf-GELU, W2 h + b2, softplus (the true log(1 + e^v): the float32 definition's switch to v above 20 moves a value by e^-20 = 2e-9), then
+    logbinom_depth_ref on the UNROUNDED pt: nothing between the operands and the depth is rounded to float32.  mag = sum_k p_k |c_k|."""
+    e, _ = bilinear_ref(emb, H, W)
+    x = torch.cat([_d(last), e] + ([] if rel is None else [_d(rel)]), -1)
+    h = x @ _d(w0).t() + _d(b0)
+    h = 0.5 * h * (1 + torch.erf(h * math.sqrt(0.5)))
+    pt = h @ _d(w2).t() + _d(b2)
+    pt = torch.logaddexp(pt, torch.zeros_like(pt))
+    return logbinom_depth_ref(pt, centers, H, W, min_temp, max_temp)
+
+
+def seed_bin_centers_ref(x, n_bins, lo, hi, bounded, normalize):
+    """x [..., >= n_bins] -> (ref, mag) [..., n_bins] (csrc/imageops.hip seed_bin_centers_kernel; lo, hi, 1e-3 the float32 scalars of the C ABI):
+    bounded: Bn = x + 1e-3, width_k = (hi - lo) Bn_k / sum Bn, edges = lo + running sum of the widths, centre_k = (e_k + e_k+1) / 2;
+    normalize: (centre - lo) / (hi - lo).  mag = the sum of the absolute values of the terms of an element: the running sums |lo| + sum |width| of the
+    two edges of a centre on the bounded path (|x| otherwise), and (mag + |lo|) / (hi - lo) after the normalisation"""
+    c = _d(x)[..., :n_bins]
+    lo, hi = float(f32(lo)), float(f32(hi))
+    mag = c.abs()
+    if bounded:
+        bn = c + float(f32(1e-3))
+        w = (hi - lo) * (bn / bn.sum(-1, keepdim=True))
+        zero = torch.zeros_like(w[..., :1])
+        edges = lo + torch.cumsum(torch.cat([zero, w], -1), -1)
+        emag = abs(lo) + torch.cumsum(torch.cat([zero, w.abs()], -1), -1)
+        c, mag = 0.5 * (edges[..., :-1] + edges[..., 1:]), 0.5 * (emag[..., :-1] + emag[..., 1:])
+    if normalize:
+        c, mag = (c - lo) / (hi - lo), (mag + abs(lo)) / (hi - lo)
+    return c, mag
+
+
+def bounded_bin_centers_ref(b, lo, hi):
+    """b [..., n_bins] -> (ref, mag): ref = clip(sort((hi - lo) b + lo), lo, hi) along the bins, mag per pixel = max over its bins of
+    (hi - lo) |b| + |lo| (broadcast to the bins).  Sorting is 1-Lipschitz in the sup norm -- if |u_k - v_k| <= e for every k then
+    |sort(u)_j - sort(v)_j| <= e for every j (the j-th smallest of v lies between the j-th smallest of u - e and of u + e) -- and so is clipping:
+    every sorted, clipped element is within the largest error of the unsorted elements of its pixel, which k 2^-24 max_k mag_k bounds."""
+    bd = _d(b)
+    lo, hi = float(f32(lo)), float(f32(hi))
+    ref = torch.clip(torch.sort((hi - lo) * bd + lo, dim=-1)[0], lo, hi)
+    mag = ((hi - lo) * bd.abs() + abs(lo)).amax(-1, keepdim=True).expand_as(ref)
+    return ref, mag
 
 
 # ---------------- inputs and cases shared by the CPU and the GPU test ----------------
@@ -356,3 +403,132 @@ ROI_FEATS = [(4, 6, 64), (28, 37, 64), (112, 154, 32)]
 # inside, touching the far corner, partly outside (x1 > W), wholly outside (negative); image coordinates of a 112 x 154 map
 ROIS = [[0, 0.0, 0.0, 77.0, 56.0], [0, 77.0, 56.0, 154.0, 112.0], [0, 38.5, 28.0, 115.5, 84.0], [0, 100.25, 60.5, 177.25, 116.5],
         [0, -90.0, -70.0, -13.0, -14.0]]
+
+
+# ---------------- operands of the metric-bins tail, the bin centres and the copies (tests/test_f64_image_ref_cpu.py, tests/test_tail_grade_gpu.py) ----
+MIN_TEMP, MAX_TEMP = 0.0212, 50.0
+TAIL_KINDS = ("random", "sorted", "t_low", "t_high", "p_ends", "softplus_linear")
+# B, H, W: one pixel; one partial group of 16; a tail of 4; one row; more pixel groups than the 512 x 4 the grid covers in one pass (tail of 14)
+TAIL_SHAPES = [(1, 1, 1), (1, 3, 5), (2, 37, 50), (1, 1, 40), (1, 150, 221)]
+TAIL_EMB_GRID, TAIL_CEN_GRID = (21, 29), (11, 15)
+# name -> (emb grid, centres grid) at 2 x 37 x 50; None = the output's own size (scale exactly 1)
+TAIL_GRIDS = {"emb_full_size": ((37, 50), TAIL_CEN_GRID), "emb_1x1": ((1, 1), TAIL_CEN_GRID), "cen_on_emb_grid": (TAIL_EMB_GRID, TAIL_EMB_GRID)}
+
+
+def tail_operands(kind, ctot, B, H, W, emb_grid=TAIL_EMB_GRID, cen_grid=TAIL_CEN_GRID, seed=0):
+    """seeded operands of the fused tail -> dict(last [B, H, W, 32], rel [B, H, W, 8] or None (ctot 160), emb [B, he, we, 128], w0 [80, ctot] over the
+    CLB buffer's channel order (last, embedding, rel), b0, w2 [4, 80], b2, centers [B, hc, wc, 64]), float32.  Kinds:
+      random           N(0, 1) features, weights N(0, 1 / fan-in), biases 0.1 N(0, 1); centres uniform in [0.5, 5.5), independent per position and bin, NOT sorted
+      sorted           the same with the centres sorted along the bins (tests/op_checks.py bins_tail)
+      t_low, t_high    b2 -+ 30 on t0 and +- 30 on t1: t0 / (t0 + t1) is 3e-6 / 1 - 3e-6, the temperature min_temp / max_temp
+      p_ends           hidden channels 0 and 1 see only +-last[..., 0], which is +50 in the first half of the pixels and -50 in the second, and drive
+                       (p0, p1) to (50, 0) / (0, 50): 1 - p, then p, lies below the 1e-4 clamp
+      softplus_linear  b2 + (20, 20.5) on p0, p1: about half of their pre-activations above 20, where softplus is the identity"""
+    assert kind in TAIL_KINDS and ctot in (160, 168)
+    g = torch.Generator().manual_seed(1000 * TAIL_KINDS.index(kind) + ctot + 7 * H + W + seed)
+    (he, we), (hc, wc) = emb_grid, cen_grid
+    r = lambda *s: torch.randn(*s, generator=g)
+    o = dict(last=r(B, H, W, 32), rel=r(B, H, W, 8) if ctot == 168 else None, emb=r(B, he, we, 128), w0=r(80, ctot) / ctot ** 0.5, b0=0.1 * r(80),
+             w2=r(4, 80) / 80 ** 0.5, b2=0.1 * r(4), centers=torch.rand(B, hc, wc, 64, generator=g) * 5 + 0.5)
+    if kind == "sorted":
+        o["centers"] = o["centers"].sort(-1).values.contiguous()
+    if kind in ("t_low", "t_high"):
+        s = -30.0 if kind == "t_low" else 30.0
+        o["b2"][2] += s
+        o["b2"][3] -= s
+    if kind == "p_ends":
+        first = (torch.arange(B * H * W) < (B * H * W + 1) // 2).view(B, H, W)
+        o["last"][..., 0] = torch.where(first, 50.0, -50.0)
+        o["w0"][:, 0] = 0
+        o["w0"][:2] = 0
+        o["w0"][0, 0], o["w0"][1, 0] = 1.0, -1.0
+        o["b0"][:2] = 0
+        o["w2"][:, :2] = torch.tensor([[1.0, -1.0], [-1.0, 1.0], [0.0, 0.0], [0.0, 0.0]])
+    if kind == "softplus_linear":
+        o["b2"][0] += 20.0
+        o["b2"][1] += 20.5
+    return o
+
+
+def tail_ref(o, H, W):
+    return bins_tail_ref(o["last"], o["rel"], o["emb"], o["w0"], o["b0"], o["w2"], o["b2"], o["centers"], H, W, MIN_TEMP, MAX_TEMP)
+
+
+def tail_pack(o):
+    """-> packing.BinsTail of the two layers (with .mlp0 / .mlp2, the packed layers of the unfused route)"""
+    from patchfusion_amd import packing as pk
+    mlp0 = pk.pack_conv(o["w0"][:, :, None, None].clone(), o["b0"].clone(), dtype=torch.float32)
+    mlp2 = pk.pack_conv(o["w2"][:, :, None, None].clone(), o["b2"].clone(), dtype=torch.float32)
+    tw = pk.bins_tail_weights(mlp0, mlp2, 128)
+    assert tw is not None and tw.nq == (11 if o["rel"] is not None else 10)
+    return tw
+
+
+def tail_clb(o, ld=None, off=0, device="cpu"):
+    """the CLB buffer of the operands: [B, H, W, ctot] = last | NaN (the embedding slice, which the fused kernel must not read) | rel, as channels
+    [off, off + ctot) of a NaN-filled buffer of ld channels (ld None: ctot, contiguous)"""
+    B, H, W, _ = o["last"].shape
+    ctot = o["w0"].shape[1]
+    wide = torch.full((B, H, W, ld or ctot), float("nan"))
+    wide[..., off:off + 32] = o["last"]
+    if o["rel"] is not None:
+        wide[..., off + 160:off + 168] = o["rel"]
+    return wide.to(device)[..., off:off + ctot]
+
+
+def seed_operands(shape, n_bins, ld, seed=23):
+    """relu(N(0, 1)) [*shape, n_bins] (the SeedBinRegressor's activation output, with exact zeros) as channels [0, n_bins) of a NaN-filled [*shape, ld]"""
+    wide = torch.full((*shape, ld), float("nan"))
+    wide[..., :n_bins] = torch.relu(torch.randn(*shape, n_bins, generator=torch.Generator().manual_seed(seed + n_bins)))
+    return wide[..., :n_bins]
+
+
+def bounded_operands(npix, n_bins, seed=24):
+    """[1, 1, npix, n_bins]: 0.5 + 0.6 N(0, 1) (a fifth outside [0, 1], unsorted); the first min(4, npix / 2) pixels rounded to integers (ties, and
+    values outside [0, 1]); +0 and -0 in the first pixel, one bin set to the largest of its pixel in the second (a tie at the top)"""
+    b = 0.5 + 0.6 * torch.randn(1, 1, npix, n_bins, generator=torch.Generator().manual_seed(seed + n_bins + npix))
+    b[0, 0, :min(4, npix // 2)] = b[0, 0, :min(4, npix // 2)].round()
+    b[0, 0, 0, 0], b[0, 0, 0, -1] = 0.0, -0.0
+    if npix > 1:
+        b[0, 0, 1, 0] = b[0, 0, 1].max()
+    return b
+
+
+def bf16_edge_values():
+    """float32 values whose rounding to bfloat16 separates round-to-nearest-even from truncation and from round-half-up: exact ties above an even and
+    above an odd bfloat16 (both signs), the float32 neighbours of a tie, a tie at the top of a binade and the largest float32 below 2 (both round up
+    into the next binade)"""
+    bits = [0x3F808000, 0x3F818000, 0xBF808000, 0xBF818000, 0x3F807FFF, 0x3F808001, 0x3FFF8000, 0x3FFFFFFF]
+    return torch.tensor(bits, dtype=torch.int64).to(torch.int32).view(torch.float32)
+
+
+def copy_operands(shape, dt, seed=31):
+    """N(0, 1) [*shape] of dtype dt; a float32 tensor carries bf16_edge_values() in its first and its last elements"""
+    x = torch.randn(*shape, generator=torch.Generator().manual_seed(seed + shape[-1]))
+    if dt == torch.float32:
+        e = bf16_edge_values()
+        x.view(-1)[:e.numel()] = e
+        x.view(-1)[-e.numel():] = e
+    return x.to(dt)
+
+
+def _tail_cases():
+    """(name, kind, ctot, (B, H, W), emb grid, centres grid): every shape with random operands, every kind and every extra grid at 2 x 37 x 50; both
+    channel counts throughout"""
+    cases = []
+    for ctot in (168, 160):
+        for shp in TAIL_SHAPES:
+            cases.append((f"random_c{ctot}_{'x'.join(map(str, shp))}", "random", ctot, shp, TAIL_EMB_GRID, TAIL_CEN_GRID))
+        for kind in TAIL_KINDS[1:]:
+            cases.append((f"{kind}_c{ctot}_2x37x50", kind, ctot, (2, 37, 50), TAIL_EMB_GRID, TAIL_CEN_GRID))
+        for name, (eg, cg) in TAIL_GRIDS.items():
+            cases.append((f"{name}_c{ctot}_2x37x50", "random", ctot, (2, 37, 50), eg, cg))
+    return cases
+
+
+TAIL_CASES = _tail_cases()
+# lo, hi of the counted bin-centre checks: hi - lo is a float32 number, so the two roundings counted (the product and the sum, or the difference and
+# the quotient) are all there are; at the head's own 1e-3, 80 the float32 difference 79.999 is itself rounded (0.8 * 2^-24), a third rounding that an
+# unfused float32 evaluation adds to its two
+EXACT_RANGES = [(2.0 ** -10, 80.0), (-2.5, 10.0)]
+K_BOUNDED, K_SEED_NORM = 2, 2
