@@ -135,8 +135,15 @@ int pf_conv_winograd_f16x2_supported_ex(const pf_conv_params* p, int u_rows, int
  * (bias -> act -> scale -> res -> res2, all float32), and stores one of: float32 [M][y_ld] (out_f32); three bf16 planes, row-major [3][M][y_ld]
  * (y_bstride); or, with korder bit 16, two fp16 chunk-major planes [2][Cout/32][M][32] of y / 2^out_exp[n] (y_ld == Cout, Cout % 32 == 0,
  * p->out_exp required); or, with korder bit 32, two fp16 ROW-major planes [2][M][y_ld] (y_bstride) of y / 2^out_exp[n] (p->out_exp required):
- * q / k / v for pf_vit_attention_f16x2, which reads token rows.  Bits 16 and 32 exclude each other.  No batch. */
+ * q / k / v for pf_vit_attention_f16x2, which reads token rows.  Bits 16 and 32 exclude each other.  No batch.
+ * float32 output also has a 160 x 256 tile form (csrc/gemm_f16x2_t160.hip: same products in the same order, same bits); pf_gemm_f16x2_route
+ * tells which one a call runs. */
 int pf_gemm_f16x2(const pf_conv_params* p, void* stream);
+/* which tile form pf_gemm_f16x2 runs on a chip of `cus` compute units (no launch, no GPU needed): PF_S3_ROUTE_PERSIST192 or PF_S3_ROUTE_TILE160.
+ * The 160 x 256 form takes float32-output calls whose rounds of tiles x tile cost (60 MFMAs per chunk and wave against 54) come out lower:
+ * ceil(t160 / cus) * 60 < ceil(t192 / cus) * 54.  PF_F16_TILE (read per call): 0 = 192 x 192 everywhere, 1 = 160 x 256 wherever it is legal
+ * (float32 output).  -1 for a NULL p or cus <= 0. */
+int pf_gemm_f16x2_route(const pf_conv_params* p, int cus);
 
 /* FUSED Winograd F(4x4, 3x3) (csrc/wino_fused.hip): the same layers in ONE kernel -- the transformed input and the transform-domain
  * products never exist in HBM.  `p` as for pf_conv_winograd (p->w is not read); `up` = the filters in MFMA fragment order
@@ -180,6 +187,7 @@ int pf_gemm_split3_ex(const pf_conv_params* p, int grid_cap, void* stream);
 #define PF_S3_ROUTE_TILE128 1
 #define PF_S3_ROUTE_PERSIST128 2
 #define PF_S3_ROUTE_PERSIST192 3
+#define PF_S3_ROUTE_TILE160 4 /* pf_gemm_f16x2_route only: the persistent 160 x 256 fp16x2 form */
 int pf_gemm_split3_route(const pf_conv_params* p, int cus);
 int pf_gemm_split3_timed(const pf_conv_params* p, int iters, float* ms, void* stream);
 /* A plain bf16 linear layer (x [M][x_ld] bf16, w from packing.pack_conv, bf16 residuals / output, float32 output when out_f32) through the same

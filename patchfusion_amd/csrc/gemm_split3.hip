@@ -1350,8 +1350,34 @@ extern "C" int pf_gemm_f16x2_points_route_ex(const pf_conv_params* p, int cus, i
   return f16x2_points_route(*p, cus, maxima_given != 0);
 }
 
+// the 160 x 256 tile form of the fp16x2 linear (csrc/gemm_f16x2_t160.hip)
+int pf_launch_f16x2_tile160(const pf_conv_params& p, int cus, hipStream_t st);
+
 namespace {
+
+// Which tile form runs a (validated) fp16x2 linear on a chip of `cus` compute units (pf_gemm_f16x2_route exposes it to the CPU tests).  Both forms
+// give the same bits; the choice is rounds of tiles per CU x cost of a tile, a 160 x 256 tile costing 60 MFMAs per chunk and wave against the 54
+// of a 192 x 192 tile.  At 256 CUs and 8296 rows: N = 1024 (fc2, proj) is 264 tiles of 192 = two rounds (108) against 208 tiles of 160 x 256 =
+// one (60); N = 3072 is 704 / 624 tiles, three rounds either way, N = 4096 968 / 832, four rounds either way: 192 stays.  1037 rows: one round
+// either way.  Plane outputs (korder bits 16 / 32, three bf16 planes) exist on the 192-tile form only.  PF_F16_TILE (A/B and tests, read per call):
+// 0 = 192 everywhere, 1 = 160 x 256 wherever it is legal.
+int f16x2_route(const pf_conv_params& p, int cus) {
+  const char* s = getenv("PF_F16_TILE");
+  const char mode = s ? s[0] : 'r';
+  if (mode == '0' || !p.out_f32 || (p.korder & 48) || p.batch > 1) return PF_S3_ROUTE_PERSIST192;
+  if (mode == '1') return PF_S3_ROUTE_TILE160;
+  const long M = (long)p.B * p.OH * p.OW;
+  const long t192 = ((M + 191) / 192) * ((p.Cout + 191) / 192), t160 = ((M + 159) / 160) * ((p.Cout + 255) / 256);
+  const long cost192 = ((t192 + cus - 1) / cus) * 54, cost160 = ((t160 + cus - 1) / cus) * 60;
+  return cost160 < cost192 ? PF_S3_ROUTE_TILE160 : PF_S3_ROUTE_PERSIST192;
+}
+
 }  // namespace
+
+extern "C" int pf_gemm_f16x2_route(const pf_conv_params* p, int cus) {
+  if (!p || cus <= 0) return -1;
+  return f16x2_route(*p, cus);
+}
 
 extern "C" int pf_gemm_split3(const pf_conv_params* p, void* stream) { return pf_gemm_split3_ex(p, 0, stream); }
 
@@ -1433,6 +1459,7 @@ extern "C" int pf_gemm_f16x2(const pf_conv_params* p, void* stream) {
   if (!p->out_f32 && p->y_bstride <= 0) return PF_ERR_ARG;
   if ((p->korder & 16) && (!p->out_exp || p->y_ld != p->Cout || p->Cout % 32)) return PF_ERR_ARG;
   if ((p->korder & 32) && (!p->out_exp || p->y_ld < p->Cout || p->y_bstride % 4 || (reinterpret_cast<size_t>(p->y) & 7))) return PF_ERR_ARG;   // 8-byte stores
+  if (f16x2_route(*p, cu_count()) == PF_S3_ROUTE_TILE160) return pf_launch_f16x2_tile160(*p, cu_count(), reinterpret_cast<hipStream_t>(stream));
   return launch_persist192_f16_linear(*p, reinterpret_cast<hipStream_t>(stream));
 }
 

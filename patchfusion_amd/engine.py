@@ -44,15 +44,17 @@ def vit_f16x2_enabled(crops):
 def vit_attn_f16x2_enabled():
     """with the fp16x2 block linears (vit_f16x2_enabled): also run the attention and the projection on two scaled fp16 planes (csrc/attn_split3.hip
     pf_vit_attention_f16x2, the projection through pf_gemm_f16x2)?  PF_VIT_ATTN_F16X2: 0 = the round-8 block (fp16x2 qkv / fc1 / fc2, bf16x3
-    attention and projection); 1 (default) = q / k / v on two fp16 planes and the fp16x2 attention, which writes the three bf16 planes of a
-    projection that stays on bf16x3; 2 = the attention's output and the projection on two fp16 planes as well.  Measured per launch at
-    8 x 1037 tokens (profiles/r10_attn_f16x2_launches.md): attention 1.54x (three bf16 planes out) / 1.59x (two fp16 planes out), the fp16x2
-    projection 0.96-0.98x of the bf16x3 one -- not faster, so it moves only on request.  Image pass, two engines, built in both orders
-    (profiles/r10_attn_f16x2_image_ab.md): 1 gains 3.0 ms over 0 in the mean of the two orders.  Read once per engine build; crops branch only.
+    attention and projection); 1 = q / k / v on two fp16 planes and the fp16x2 attention, which writes the three bf16 planes of a
+    projection that stays on bf16x3; 2 (default) = the attention's output and the projection on two fp16 planes as well.  Measured per launch at
+    8 x 1037 tokens: attention 1.54x (three bf16 planes out) / 1.59x (two fp16 planes out) (profiles/r10_attn_f16x2_launches.md); the fp16x2
+    projection was 0.96-0.98x of the bf16x3 one on 192 x 192 tiles (264 tiles on 256 CUs: two tile times) and is 2.1x on the 160 x 256 tile that
+    pf_gemm_f16x2 now routes it to (0.0545 ms against 0.1147, profiles/r13_tile160_linears.md).  Image pass (profiles/r13_tile160_image_ab.md):
+    2 on the new tile gains 3.2 ms over the 192-tile tree between alternating processes (3.2 times the largest within-arm spread) and 5.4 ms in
+    the mean of both engine build orders in one process; max |depth difference| 4.8e-7.  Read once per engine build; crops branch only.
     -> 0, 1 (attention) or 2 (attention and projection)"""
     import os
-    v = os.environ.get("PF_VIT_ATTN_F16X2", "1")
-    return 0 if v == "0" else 2 if v == "2" else 1
+    v = os.environ.get("PF_VIT_ATTN_F16X2", "2")
+    return 0 if v == "0" else 1 if v == "1" else 2
 
 
 def attention_split3_enabled():

@@ -3,6 +3,12 @@ usage: python tools/vit_f16x2_ab.py linears            each linear at the pass's
                                                         then R rounds of 20 launches per route; best round), producer LayerNorm timed alongside
        python tools/vit_f16x2_ab.py image [--steps K] [--rounds R]   whole image pass (BASELINE configs[2]), one engine per route (PF_VIT_F16X2 is read
                                                         at engine build), routes interleaved round by round; max |depth difference|
+       python tools/vit_f16x2_ab.py tiles              the 160 x 256 tile form (csrc/gemm_f16x2_t160.hip, PF_F16_TILE=1) against the 192 x 192 form (=0) per launch at
+                                                        8296 rows, float32 out: fc2 and proj (also on the bf16x3 128-tile route), qkv's and fc1's shapes; every round printed
+       python tools/vit_f16x2_ab.py fc2                six fc2 launches (8296 rows) on each tile form and nothing else: the target of a counter run
+                                                        (rocprofv3 --pmc ... -- python tools/vit_f16x2_ab.py fc2, no tracing beside it)
+       python tools/vit_f16x2_ab.py tile_image [--steps K] [--rounds R] [--reverse]   whole image pass, three arms interleaved round by round: PF_F16_TILE=0 (192-tiles everywhere),
+                                                        default routing (fc2 on the new tile), default routing with PF_VIT_ATTN_F16X2=2 (fc2 and an fp16x2 proj)
        python tools/vit_f16x2_ab.py slack [--wide]      per layer log2(static bound / observed max) of the K-side operands over one image pass
                                                         (min and median over channels); --wide: tests/dynamic_range.py weights"""
 import argparse
@@ -80,6 +86,122 @@ def linears(rounds):
                 if rnd:
                     best[i] = min(best[i], t)
         print(f"| LayerNorm -> planes {D} | {M} | {best[0]:.4f} | {best[1]:.4f} | {best[0] / best[1]:.2f}x |", flush=True)
+
+
+def tiles(rounds):
+    from patchfusion_amd import packing as pk
+    from patchfusion_amd.hip_ops import ops
+    g = torch.Generator().manual_seed(0)
+    D, M = 1024, 8 * 1037
+    print("| op | arm | " + " | ".join(f"round {r} ms" for r in range(rounds)) + " | best ms |")
+    print("|---|---|" + "---|" * (rounds + 1))
+    for name, K, N, res, scale in (("fc2", 4 * D, D, True, True), ("proj", D, D, True, True), ("qkv shape, float32 out", D, 3 * D, False, False),
+                                   ("fc1 shape, float32 out", D, 4 * D, False, False)):
+        w = torch.randn(N, K, generator=g) / K ** 0.5
+        b = torch.randn(N, generator=g)
+        sc = (0.5 + torch.rand(N, generator=g)) if scale else None
+        pw3 = pk.pack_conv_split3(w, b, scale=sc, kmajor=True).to(DEV)
+        pw2 = pk.pack_conv_f16x2(w, b, sc, torch.full((K,), 8.0, dtype=torch.float64)).to(DEV)
+        x3 = torch.randn(3, K // 32, M, 32, generator=g).to(torch.bfloat16).to(DEV)
+        x2 = torch.randn(2, K // 32, M, 32, generator=g).to(torch.float16).to(DEV)
+        r = torch.randn(M, N, generator=g).to(DEV) if res else None
+        y = torch.empty(M, N, device=DEV)
+
+        def f16(tile):
+            def run():
+                os.environ["PF_F16_TILE"] = tile
+                ops.conv_f16x2(x2, pw2, y, res=r)
+            return run
+        arms = [("bf16x3 (pf_gemm_split3 route)", lambda: ops.conv_split3(x3, pw3, y, res=r)), ("fp16x2 192 x 192", f16("0")), ("fp16x2 160 x 256", f16("1"))]
+        times = [[] for _ in arms]
+        for rnd in range(rounds + 1):
+            for i, (_, f) in enumerate(arms):
+                t = _timed(f)
+                if rnd:
+                    times[i].append(t)
+        for (an, _), ts in zip(arms, times):
+            print(f"| {name} {K}->{N} | {an} | " + " | ".join(f"{t:.4f}" for t in ts) + f" | {min(ts):.4f} |", flush=True)
+    os.environ.pop("PF_F16_TILE", None)
+
+
+def fc2_only():
+    from patchfusion_amd import packing as pk
+    from patchfusion_amd.hip_ops import ops
+    g = torch.Generator().manual_seed(0)
+    D, M = 1024, 8 * 1037
+    K, N = 4 * D, D
+    pw2 = pk.pack_conv_f16x2(torch.randn(N, K, generator=g) / K ** 0.5, torch.randn(N, generator=g), 0.5 + torch.rand(N, generator=g),
+                             torch.full((K,), 8.0, dtype=torch.float64)).to(DEV)
+    x2 = torch.randn(2, K // 32, M, 32, generator=g).to(torch.float16).to(DEV)
+    r = torch.randn(M, N, generator=g).to(DEV)
+    y = torch.empty(M, N, device=DEV)
+    for tile in ("0", "1"):
+        os.environ["PF_F16_TILE"] = tile
+        for _ in range(6):
+            ops.conv_f16x2(x2, pw2, y, res=r)
+        torch.cuda.synchronize()
+    os.environ.pop("PF_F16_TILE", None)
+
+
+def tile_image(steps, rounds, reverse=False):
+    from patchfusion_amd.config import make_config
+    from patchfusion_amd.spec import patchfusion_spec, synthetic_state_dict
+    dev = torch.device("cuda", 0)
+    cfg = make_config("vitl", (392, 518), (2160, 3840), (4, 4))
+    sd = synthetic_state_dict(patchfusion_spec(cfg), 0)
+    img = torch.rand(1, 3, 2160, 3840, generator=torch.Generator().manual_seed(1234)).to(dev)
+    os.environ.pop("PF_F16_TILE", None)
+    models = {}
+    # PF_VIT_ATTN_F16X2 is read when the engine is built (first forward); PF_F16_TILE per call.  The engine built second has run slower whichever arm
+    # it holds (profiles/r10_attn_f16x2_image_ab.md): --reverse builds the PF_VIT_ATTN_F16X2=2 engine first, and a verdict on that arm needs both orders
+    for v in (("2", "1") if reverse else ("1", "2")):
+        os.environ["PF_VIT_ATTN_F16X2"] = v
+        m = _model(sd, cfg, dev)
+        lr = m.resizer(img)
+        m(mode="infer", image_lr=lr, image_hr=img, cai_mode="m1", process_num=8)
+        torch.cuda.synchronize()
+        models[v] = m
+    os.environ.pop("PF_VIT_ATTN_F16X2", None)
+    assert [models[v]._engine["fine"].proj_f16x2 for v in ("1", "2")] == [False, True]
+    arms = [("PF_F16_TILE=0, PF_VIT_ATTN_F16X2=1 (the 192-tile everywhere)", "1", "0"), ("default routing, PF_VIT_ATTN_F16X2=1 (fc2 moves)", "1", None),
+            ("default routing, PF_VIT_ATTN_F16X2=2 (fc2 and proj move)", "2", None)]
+
+    def run(arm):
+        _, eng, tile = arm
+        if tile is None:
+            os.environ.pop("PF_F16_TILE", None)
+        else:
+            os.environ["PF_F16_TILE"] = tile
+        d, _ = models[eng](mode="infer", image_lr=lr, image_hr=img, cai_mode="m1", process_num=8)
+        return d
+    for arm in arms:                                     # one untimed round
+        run(arm)
+    torch.cuda.synchronize()
+    times, outs = [[] for _ in arms], [None for _ in arms]
+    for r in range(rounds):
+        for i, arm in enumerate(arms):
+            outs[i] = run(arm).clone()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                run(arm)
+            torch.cuda.synchronize()
+            times[i].append((time.perf_counter() - t0) / steps * 1e3)
+            print(f"round {r} {arm[0]}: {times[i][-1]:.2f} ms", file=sys.stderr, flush=True)
+    os.environ.pop("PF_F16_TILE", None)
+    print("| arm | " + " | ".join(f"round {r} ms" for r in range(rounds)) + " | mean ms | spread ms | vs arm 0 | max abs depth diff vs arm 0 |")
+    print("|---|" + "---|" * (rounds + 4))
+    m0 = sum(times[0]) / rounds
+    for i, arm in enumerate(arms):
+        m = sum(times[i]) / rounds
+        print(f"| {arm[0]} | " + " | ".join(f"{t:.2f}" for t in times[i]) + f" | {m:.2f} | {max(times[i]) - min(times[i]):.2f} | {m - m0:+.2f} | "
+              f"{float((outs[i] - outs[0]).abs().max()):.3e} |")
+    spread = max(max(t) - min(t) for t in times)
+    for i in range(1, len(arms)):
+        gain = m0 - sum(times[i]) / rounds
+        print(f"\narm {i} against arm 0: gain {gain:.2f} ms, largest within-arm spread {spread:.2f} ms, ratio {gain / spread:.1f} (rule: >= 3)")
+    print(f"\n{steps} images per cell, split 4x4, process_num 8, depth max {float(outs[0].abs().max()):.3f}; engines built in the order "
+          f"PF_VIT_ATTN_F16X2={'2, 1' if reverse else '1, 2'}")
 
 
 def _model(sd, cfg, dev):
@@ -194,14 +316,21 @@ def slack(wide):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=("linears", "image", "slack"))
+    ap.add_argument("mode", choices=("linears", "tiles", "fc2", "tile_image", "image", "slack"))
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--wide", action="store_true")
+    ap.add_argument("--reverse", action="store_true", help="tile_image: build the PF_VIT_ATTN_F16X2=2 engine first")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     if a.mode == "linears":
         linears(a.rounds)
+    elif a.mode == "tiles":
+        tiles(a.rounds)
+    elif a.mode == "fc2":
+        fc2_only()
+    elif a.mode == "tile_image":
+        tile_image(a.steps, a.rounds, a.reverse)
     elif a.mode == "image":
         image(a.steps, a.rounds)
     else:
