@@ -426,7 +426,8 @@ int pf_depth_to_u16(const float* depth, long n, float scale, uint16_t* out, void
  * edges (or NULL) = disp_gt_edges, non-zero = boundary pixel; additional_mask (or NULL) = [H][W] bytes, zero = excluded
  * (metric.py:128-130, prompt-depth evaluation).  Terms in float32 like numpy, sums in double:
  * out13 = n, #(thresh<1.25), #(<1.25^2), #(<1.25^3), S|gt-p|/gt, S(gt-p)^2/gt, S(gt-p)^2, S(ln gt - ln p)^2,
- *         S(ln p - ln gt), S(ln p - ln gt)^2, S|log10 gt - log10 p|, S soft-edge error, #(mask & edges)   (device) */
+ *         S(ln p - ln gt), S(ln p - ln gt)^2, S|log10 gt - log10 p|, S soft-edge error, #(mask & edges)   (device)
+ * A NaN in gt is invalid itself but makes the soft-edge minimum of its eight neighbours NaN, as np.minimum.reduce does. */
 int pf_depth_metrics(const float* gt, int H, int W, const float* pred, int ph, int pw, const float* edges,
                      const uint8_t* additional_mask, float min_depth, float max_depth, int crop_y0, int crop_y1, int crop_x0, int crop_x1,
                      double* out13, void* stream);

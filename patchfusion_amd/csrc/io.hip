@@ -366,15 +366,17 @@ __global__ __launch_bounds__(256) void depth_metrics_kernel(const float* __restr
     s[10] += (double)fabsf(log10f(g) - log10f(p));
     if (edges && edges[i] != 0.f) {
       float m = 3.4e38f;
+      bool unordered = false;                          // a NaN neighbour makes the minimum NaN, as np.minimum.reduce does (fminf would drop it)
 #pragma unroll
       for (int dy = -1; dy <= 1; ++dy)
 #pragma unroll
         for (int dx = -1; dx <= 1; ++dx) {
           const int yy = y - dy, xx = x - dx;          // shift_2d_replace: shifted[y][x] = gt[y-dy][x-dx], 0 outside
           const float gs = ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) ? gt[(long)yy * W + xx] : 0.f;
+          unordered |= gs != gs;
           m = fminf(m, fabsf(gs - p));
         }
-      s[11] += (double)m;
+      s[11] += (double)(unordered ? __builtin_nanf("") : m);
       s[12] += 1.0;
     }
   }
