@@ -53,7 +53,7 @@ typedef struct {
   int act;       /* PF_ACT_* */
   int relu_in;   /* apply ReLU to x on load (ResidualConvUnit, blocks.py:78,83) */
   int out_f32;   /* store float32 even when dtype == bf16 (bins-head tensors) */
-  int shuffle;   /* s>1: ConvTranspose2d(kernel=stride=s): N = s*s*Cout_t, y is [B,OH*s,OW*s,Cout_t] */
+  int shuffle;   /* 1 = none; s>1: ConvTranspose2d(kernel=stride=s): N = s*s*Cout_t, y is [B,OH*s,OW*s,Cout_t]; 0 and negative values are refused */
   int dtype;
   int korder;    /* K order of w: 0 = (ky,kx,c); 1 = (c/32, ky, kx, c%32), f32 only, Cin % 32 == 0 (see packing.py) */
   int batch;     /* > 1: that many independent GEMM planes in ONE launch (float32, no bias / scale / residual): plane k reads
@@ -63,9 +63,18 @@ typedef struct {
   const int* col_exp;  /* fp16x2 linears only (pf_gemm_f16x2): int32 column exponents f_n [w_rows], y = ldexp(acc, f_n) before the epilogue */
   const int* out_exp;  /* fp16x2 linears with fp16x2 planes out: int32 exponents of the consumer's input channels [Cout] */
 } pf_conv_params;
+/* pf_conv: Refused (PF_ERR_ARG): a null p / x / w / y; x or w off a 16-byte boundary, y off four of its elements, bias / scale / res / res2 off one
+ * element (residual views one element off a vector boundary are computed); a dtype other than 0 / 1, an act outside PF_ACT_*, shuffle < 1 (1 = none),
+ * batch < 0 or > 65535; B, H, W, OH, OW, KH, KW, stride not positive, pad < 0, OH / OW other than (H + 2 pad - KH) / stride + 1 and (W + 2 pad - KW) /
+ * stride + 1; Cin not a positive multiple of the 16-byte vector, x_ld not such a multiple or below Cin; Cout not a positive multiple of 4, y_ld / res_ld
+ * / res2_ld not multiples of 4 or below the channels of a pixel (Cout, Cout / s^2 for y under the pixel shuffle); Kpad not a positive multiple of the
+ * 128-byte chunk or below KH KW Cin; w_rows < Cout; more than 16 taps; B OH OW >= 2^31; korder other than 0, or 1 outside float32 with Cin % 32 == 0;
+ * batch > 1 with bf16, shuffle, bias, scale, a residual or a missing plane stride; shuffle > 1 with a filter other than 1 x 1, a residual, or Cout / s^2
+ * not a multiple of 4. */
 int pf_conv(const pf_conv_params* p, void* stream);
 /* timing helper for the roofline entry of bench.py: runs `iters` launches bracketed by HIP events on
  * `stream`, returns the average milliseconds per launch in *ms */
+/* pf_conv_timed: Refused (PF_ERR_ARG): as pf_conv, and a null ms or iters <= 0. */
 int pf_conv_timed(const pf_conv_params* p, int iters, float* ms, void* stream);
 /* Introspection for the tests: the kernel variant that the calling thread's last pf_conv launched (0 before the first launch).  Read-only; no
  * dispatch rule reads it and nothing is launched.  code = family * 10^8 + shape * 100 + shuffle * 10 + relu_in, shuffle = 0 | 2 | 4 ..., with
@@ -83,16 +92,23 @@ int pf_conv_last_variant(void);
  * (patchfusion_amd/packing.py winograd_filters); V, M = device workspaces of (m+2)^2 * T * Cin and (m+2)^2 * T * Cout floats,
  * T = B * ceil(H/m) * ceil(W/m).  Input transform -> (m+2)^2 GEMMs through pf_conv -> output transform + epilogue (winograd.hip).
  * m = 2 multiplies 2.25x less than the direct convolution at ~2.5x its float32 rounding error, m = 4 4x less at ~15x. */
+/* pf_conv_winograd: Refused (PF_ERR_ARG): a null p / x / y / U / V / M or one of them (or bias / res / res2) off a 16-byte boundary; anything but a
+ * float32 3 x 3 / stride 1 / pad 1 layer with shuffle 1 and no scale; B, H, W not positive, OH != H, OW != W; Cin not a positive multiple of 32, Cout of
+ * 8; x_ld / y_ld / res_ld / res2_ld not multiples of 4 or below their channels; act other than NONE / RELU; B H W >= 2^31; m other than 2 / 4; u_rows <
+ * Cout, u_kpad < Cin or not a multiple of 32. */
 int pf_conv_winograd(const pf_conv_params* p, int m, const void* U, int u_rows, int u_kpad, void* V, void* M, void* stream);
 /* The same three steps with the transform-domain GEMM in split precision (m = 4): V3 = workspace of 3 x 36 x T x Cin bf16 (the input transform
  * writes the three planes, chunk-major: [3][36][Cin/32][T][32]), U3 = the three bf16 planes of G g G^T, chunk-major [3][36][Cin/32][u_rows][32]
  * (patchfusion_amd/packing.py PackedConv.wino_u3; u_kpad must equal Cin), M = 36 x T x Cout float32; one batched pf_gemm_split3 launch
  * (korder = 6) between the transforms. */
+/* pf_conv_winograd_split3: Refused (PF_ERR_ARG): as pf_conv_winograd for p and the pointers; u_rows < Cout, u_kpad != Cin. */
 int pf_conv_winograd_split3(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, void* V3, void* M, void* stream);
 /* the same layer `window` Winograd tiles at a time (window % 8 == 0; 0 = all tiles at once): V3 / M then are arenas for ONE window (3 x 36 x window x Cin
  * bf16, 36 x window x Cout float32) that every window reuses -- small windows keep the pair inside the 256 MB memory-side cache.  Tiles are independent:
  * identical results for every window.  With more than one window the output of window k is written before the input of window k + 1 (and its one-pixel
  * halo) is read: x and y must NOT overlap then (PF_ERR_ARG); a residual may alias y (it is read at the pixels being written). */
+/* pf_conv_winograd_split3_windowed: Refused (PF_ERR_ARG): as pf_conv_winograd_split3; window < 0 or not a multiple of 8; x and y overlapping when the
+ * layer takes more than one window. */
 int pf_conv_winograd_split3_windowed(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, void* V3, void* M, long window, void* stream);
 /* fp16x2 form of the same windowed layer (csrc/wino_f16x2.hip): every operand of the transform-domain GEMM is two fp16 planes with a power-of-two
  * scale, three f16 MFMAs per product instead of six bf16 ones.  U = PackedConv.wino_u, float32 [36][u_rows][Cin] (u_kpad == Cin, u_rows % 16 == 0);
@@ -100,34 +116,50 @@ int pf_conv_winograd_split3_windowed(const pf_conv_params* p, const void* U3, in
  * bytes (per-call channel maxima of x, the scaled filter planes and their column exponents).  Same argument rules as the bf16x3 entry, the x / y alias
  * refusal included.  pf_conv_winograd_f16x2_supported returns 1 when a call qualifies and the product of the whole layer has an fp16x2 kernel
  * (pf_gemm_f16x2_points_route >= 0: the persistent 192 x 192 or 128 x 128 walk), else 0 -- the caller then takes pf_conv_winograd_split3_windowed. */
+/* pf_wino_f16x2_scratch_bytes: Answers 0 for cin <= 0 or u_rows <= 0. */
 long pf_wino_f16x2_scratch_bytes(int cin, int u_rows);
+/* pf_conv_winograd_f16x2_supported: Answers 0 for every call pf_conv_winograd_f16x2_windowed refuses on account of p, u_rows, u_kpad or window. */
 int pf_conv_winograd_f16x2_supported(const pf_conv_params* p, int u_rows, int u_kpad, long window);
+/* pf_conv_winograd_f16x2_windowed: Refused (PF_ERR_ARG): as pf_conv_winograd_split3_windowed; u_rows not a multiple of 16; Cin > 8192; a null or
+ * misaligned scratch. */
 int pf_conv_winograd_f16x2_windowed(const pf_conv_params* p, const void* U, int u_rows, int u_kpad, void* V2, void* M, void* scratch, long window,
                                     void* stream);
 /* the same call with the range pass handed from layer to layer: cmax_in = the channel maxima of x (uint32 [Cin] float bits, of relu(x) when
  * p->relu_in) as the producer's output transform merged them, or NULL = run the range pass; cmax_out = NULL or a uint32 [Cout] buffer into which this
  * layer's output transform merges max |y| per channel (of max(y, 0) when cmax_out_relu != 0); it is zeroed once per call, every window accumulates
  * into it, and it equals what the range pass computes on y bit for bit.  y is bit-identical with and without cmax_out. */
+/* pf_conv_winograd_f16x2_windowed_ex: Refused (PF_ERR_ARG): as pf_conv_winograd_f16x2_windowed; cmax_in / cmax_out off a 4-byte boundary; cmax_out ==
+ * cmax_in. */
 int pf_conv_winograd_f16x2_windowed_ex(const pf_conv_params* p, const void* U, int u_rows, int u_kpad, void* V2, void* M, void* scratch, long window,
                                        const void* cmax_in, void* cmax_out, int cmax_out_relu, void* stream);
 /* pf_conv_winograd_split3_windowed as such a producer */
+/* pf_conv_winograd_split3_windowed_ex: Refused (PF_ERR_ARG): as pf_conv_winograd_split3_windowed; cmax_out off a 4-byte boundary. */
 int pf_conv_winograd_split3_windowed_ex(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, void* V3, void* M, long window, void* cmax_out,
                                         int cmax_out_relu, void* stream);
 /* the range pass alone (the reference of the hand-over): cmax uint32 [C] must be zeroed by the caller; x float32 [P][x_ld], C % 4 == 0 */
+/* pf_wino_absmax: Refused (PF_ERR_ARG): null pointers, x off a 16-byte or cmax off a 4-byte boundary; P <= 0; C not a positive multiple of 4; x_ld not a
+ * multiple of 4 or below C. */
 int pf_wino_absmax(const void* x, int x_ld, long P, int C, int relu_in, void* cmax, void* stream);
 /* its batched product alone: x / w = two fp16 planes each, chunk-major (korder = 6, batch = transform points, no epilogue), y float32 =
  * ldexp(sum, col_exp[z][n]) with col_exp int32 [batch][w_rows] */
+/* pf_gemm_f16x2_points: Refused (PF_ERR_ARG): as pf_gemm_split3 for the linear-layer rules; a null or 16-byte-misaligned x / w / y / col_exp; korder !=
+ * 6, out_f32 == 0; x_ld != Cin, Kpad != Cin, w_rows % 4; any epilogue (bias, scale, res, res2, act); M * 64 or w_rows * 64 >= 2^31; fewer than 8 tiles
+ * in the launch. */
 int pf_gemm_f16x2_points(const pf_conv_params* p, const int* col_exp, int grid_cap, void* stream);
 /* the same product on 128 x 128 tiles (csrc/wino_f16x2_n256.hip; the 256-column layers): same operands, same result bits */
+/* pf_gemm_f16x2_points128: Refused (PF_ERR_ARG): as pf_gemm_f16x2_points (fewer than 8 tiles are accepted). */
 int pf_gemm_f16x2_points128(const pf_conv_params* p, const int* col_exp, int grid_cap, void* stream);
 /* which of the two runs the product of a whole layer on a chip of `cus` compute units: PF_S3_ROUTE_PERSIST192, PF_S3_ROUTE_PERSIST128, or -1 when
  * the layer stays on three bf16 planes (pf_gemm_split3_route gives TILE64 / TILE128, or PF_WINO_F16X2_N256=0 for the 128-tile layers, or a 128-tile layer outside the measured rule -- K >= 512 and >= 4096 tiles; =3: every one); no launch */
+/* pf_gemm_f16x2_points_route: Answers -1 for a null p or cus <= 0. */
 int pf_gemm_f16x2_points_route(const pf_conv_params* p, int cus);
 /* the same rule for a layer whose channel maxima are handed in (maxima_given != 0: no memset, no range pass).  At default switches the answer does not
  * depend on maxima_given (the wider rule measured no gain in the image pass, profiles/r12_cmax_image_ab.md); under PF_WINO_F16X2_N256=5 the 128-tile
  * layers with given maxima take fp16x2 from K >= 256 and 2128 Winograd tiles on (profiles/r11_n256_sweep.md, column "maxima given") */
+/* pf_gemm_f16x2_points_route_ex: Answers -1 for a null p or cus <= 0. */
 int pf_gemm_f16x2_points_route_ex(const pf_conv_params* p, int cus, int maxima_given);
 /* pf_conv_winograd_f16x2_supported by that rule, for a call that will pass cmax_in (maxima_given != 0) */
+/* pf_conv_winograd_f16x2_supported_ex: Answers 0 as pf_conv_winograd_f16x2_supported. */
 int pf_conv_winograd_f16x2_supported_ex(const pf_conv_params* p, int u_rows, int u_kpad, long window, int maxima_given);
 /* fp16x2 linear layer (the ViT block linears; packing.pack_conv_f16x2): x = two fp16 planes, chunk-major [2][K/32][M][32], holding x / 2^e_k;
  * w = two fp16 planes [2][K/32][w_rows][32] holding W[n][k] 2^(e_k - f_n); korder must be 6 (| 16, see below).  p->col_exp = f_n [w_rows] (required).
@@ -138,11 +170,15 @@ int pf_conv_winograd_f16x2_supported_ex(const pf_conv_params* p, int u_rows, int
  * q / k / v for pf_vit_attention_f16x2, which reads token rows.  Bits 16 and 32 exclude each other.  No batch.
  * float32 output also has a 160 x 256 tile form (csrc/gemm_f16x2_t160.hip: same products in the same order, same bits); pf_gemm_f16x2_route
  * tells which one a call runs. */
+/* pf_gemm_f16x2: Refused (PF_ERR_ARG): as pf_gemm_split3 for the linear-layer rules and the alignment of x / w / y / bias / scale / res / res2; a null
+ * or misaligned col_exp (out_exp with the plane outputs); batch > 1; korder other than 6 (| 16 | 32), bits 16 and 32 together, or either with float32
+ * output; x_ld != Cin, Kpad != Cin, w_rows % 4; korder bit 16 with y_ld != Cout or Cout % 32; M * 64 or w_rows * 64 >= 2^31. */
 int pf_gemm_f16x2(const pf_conv_params* p, void* stream);
 /* which tile form pf_gemm_f16x2 runs on a chip of `cus` compute units (no launch, no GPU needed): PF_S3_ROUTE_PERSIST192 or PF_S3_ROUTE_TILE160.
  * The 160 x 256 form takes float32-output calls whose rounds of tiles x tile cost (60 MFMAs per chunk and wave against 54) come out lower:
  * ceil(t160 / cus) * 60 < ceil(t192 / cus) * 54.  PF_F16_TILE (read per call): 0 = 192 x 192 everywhere, 1 = 160 x 256 wherever it is legal
  * (float32 output).  -1 for a NULL p or cus <= 0. */
+/* pf_gemm_f16x2_route: Answers -1 for a null p or cus <= 0. */
 int pf_gemm_f16x2_route(const pf_conv_params* p, int cus);
 
 /* FUSED Winograd F(4x4, 3x3) (csrc/wino_fused.hip): the same layers in ONE kernel -- the transformed input and the transform-domain
@@ -151,9 +187,15 @@ int pf_gemm_f16x2_route(const pf_conv_params* p, int cus);
  * super-tiles (32 output tiles: 4 x 8 or 8 x 4, picked for the least padding) per block group (L2 locality knob, >= 1), `gs` >> 16 = 0
  * or a forced super-tile width 8 | 4 (tuning aid).  Needs Cin % 16 == 0, Cin >= 32, Cout % 4 == 0, B*H*W*x_ld < 2^31:
  * pf_conv_winograd_fused_supported(p) returns 1 when `p` qualifies, else 0 (callers then take pf_conv_winograd / pf_conv). */
+/* pf_conv_winograd_fused_supported: Answers 0 also for B, H, W not positive, shuffle != 1, x_ld < Cin, y_ld / res_ld / res2_ld < Cout and x / y / bias /
+ * res / res2 off a 16-byte boundary. */
 int pf_conv_winograd_fused_supported(const pf_conv_params* p);
+/* pf_conv_winograd_fused: Refused (PF_ERR_ARG): a null p / x / y / up; whatever pf_conv_winograd_fused_supported answers 0 to (which now includes B, H,
+ * W not positive, x_ld < Cin, y_ld / res_ld / res2_ld < Cout, shuffle != 1 and x / y / bias / res / res2 off a 16-byte boundary); up off a 16-byte
+ * boundary; nnb != ceil(Cout / 64); gs < 0 or a forced super-tile width other than 0 / 4 / 8. */
 int pf_conv_winograd_fused(const pf_conv_params* p, const void* up, int nnb, int gs, void* stream);
 /* timing helper like pf_conv_timed: `iters` launches bracketed by HIP events on `stream` */
+/* pf_conv_winograd_fused_timed: Refused (PF_ERR_ARG): as pf_conv_winograd_fused, and a null ms or iters <= 0. */
 int pf_conv_winograd_fused_timed(const pf_conv_params* p, const void* up, int nnb, int gs, int iters, float* ms, void* stream);
 
 /* ---- split-precision linear layer (csrc/gemm_split3.hip; the float32 mode's ViT block linears) --------------------------------------------
@@ -170,6 +212,12 @@ int pf_conv_winograd_fused_timed(const pf_conv_params* p, const void* up, int nn
  * Kernel choice is internal and result-identical (same chunk order, same six terms per accumulator): 64 x 128 tiles below one round of tiles,
  * one 128 x 128 tile per block, or -- from two rounds of tiles on -- a PERSISTENT kernel (one block per CU walks its tiles) with 128 x 128 tiles
  * on a three-slot LDS ring or 192 x 192 tiles on a two-slot ring, whichever costs fewer rounds x tile cost. */
+/* pf_gemm_split3: Refused (PF_ERR_ARG): a null p / x / w / y; x, w, bias, scale, res, res2 off a 16-byte boundary, y off 16 bytes (float32 or chunk-
+ * major planes) / 8 bytes (row-major planes); anything but a 1 x 1 / stride 1 / pad 0 / shuffle 1 layer; B, H, W, OH, OW not positive or OH != H, OW !=
+ * W; an act outside PF_ACT_*; batch < 0 or > 65535, or > 1 with plane output or an epilogue; Cin not a positive multiple of 32, Kpad not such a multiple
+ * or below Cin, x_ld not a multiple of 8 or below Cin; Cout not a positive multiple of 4, y_ld / res_ld / res2_ld not multiples of 4 or below Cout,
+ * w_rows < Cout; M >= 2^31; x_bstride / w_bstride not positive multiples of 8, y_bstride (plane output) not a positive multiple of 4 (8 chunk-major);
+ * korder bits outside 2 | 4 | 8, bit 2 with x_ld != Cin, bit 4 with Kpad != Cin, bit 8 with float32 output, y_ld != Cout or Cout % 32. */
 int pf_gemm_split3(const pf_conv_params* p, void* stream);
 /* The same split-precision product for a 1x1 convolution / linear layer whose ACTIVATIONS are plain float32 (round 6; replaces pf_conv's f32-MFMA
  * route for the 1x1 layers of the DPT / metric-bins heads -- external/zoedepth/models/layers/localbins_layers.py:99-117, attractor.py:156-161,
@@ -178,9 +226,14 @@ int pf_gemm_split3(const pf_conv_params* p, void* stream);
  * bias / scale / res / res2 / y float32; act, relu_in as pf_conv; p->w is not read); w3 = the weight's three bf16 planes, CHUNK-MAJOR
  * [3][Cin/32][w3_rows][32] (packing.pack_conv_split3(kmajor=True); w3_rows % 16 == 0, >= Cout).  The kernel splits x in its loader (three LDS
  * planes per K chunk), so no producer has to change; error against float64 = pf_gemm_split3's (tests/op_checks.py conv1x1_split3). */
+/* pf_conv1x1_split3: Refused (PF_ERR_ARG): a null p / x / y / w3; x, y, w3, bias, scale, res, res2 off a 16-byte boundary; a dtype other than float32;
+ * the linear-layer rules of pf_gemm_split3 (1 x 1, sizes positive and consistent, act, shuffle 1); batch > 1; Cin not a positive multiple of 32, x_ld
+ * not a multiple of 4 or below Cin; Cout not a positive multiple of 4, y_ld / res_ld / res2_ld not multiples of 4 or below Cout; w3_rows < Cout or not a
+ * multiple of 16; M >= 2^31, w3_rows * 64 >= 2^31. */
 int pf_conv1x1_split3(const pf_conv_params* p, const void* w3, int w3_rows, void* stream);
 /* the same call with the persistent kernels capped at `grid_cap` blocks (0 = one per CU): the CUs left over run the kernels of OTHER streams
  * (the HBM-bound Winograd transforms of the other tile batch) beside the matrix-bound GEMM */
+/* pf_gemm_split3_ex: Refused (PF_ERR_ARG): as pf_gemm_split3. */
 int pf_gemm_split3_ex(const pf_conv_params* p, int grid_cap, void* stream);
 /* which of those kernels a call would run on a chip of `cus` compute units (no launch, no GPU needed: the dispatch rule for host-side tests) */
 #define PF_S3_ROUTE_TILE64 0
@@ -188,31 +241,49 @@ int pf_gemm_split3_ex(const pf_conv_params* p, int grid_cap, void* stream);
 #define PF_S3_ROUTE_PERSIST128 2
 #define PF_S3_ROUTE_PERSIST192 3
 #define PF_S3_ROUTE_TILE160 4 /* pf_gemm_f16x2_route only: the persistent 160 x 256 fp16x2 form */
+/* pf_gemm_split3_route: Answers -1 for a null p or cus <= 0. */
 int pf_gemm_split3_route(const pf_conv_params* p, int cus);
+/* pf_gemm_split3_timed: Refused (PF_ERR_ARG): as pf_gemm_split3, and a null ms or iters <= 0. */
 int pf_gemm_split3_timed(const pf_conv_params* p, int iters, float* ms, void* stream);
 /* A plain bf16 linear layer (x [M][x_ld] bf16, w from packing.pack_conv, bf16 residuals / output, float32 output when out_f32) through the same
  * ping-pong LDS-DMA pipeline: 256 x 128 tiles, Cin % 64 == 0.  The bf16 mode's ViT block linears at large token counts (same reference layers). */
+/* pf_gemm_bf16_pp: Refused (PF_ERR_ARG): a null p / x / w / y; x, w, bias, scale off a 16-byte boundary, y off 16 (float32) / 8 bytes, res / res2 off 8
+ * bytes; the linear-layer rules of pf_gemm_split3; a dtype other than bf16; batch > 1; Cin not a positive multiple of 64, x_ld not a multiple of 8 or
+ * below Cin, Kpad not a multiple of 8 or below Cin; Cout not a positive multiple of 4, y_ld / res_ld / res2_ld not multiples of 4 or below Cout, w_rows
+ * < Cout; M >= 2^31. */
 int pf_gemm_bf16_pp(const pf_conv_params* p, void* stream);
 /* the split producers of the ViT block: LayerNorm (layers/block.py:88-93 norm1 / norm2) and the attention output (attention.py:58-60)
  * written as three bf16 planes; arguments as pf_layernorm (plain row range) / pf_vit_attention_qkv with the plane stride in elements.
  * kmajor != 0: every output plane is CHUNK-MAJOR [cols/32][rows][32] (rows = all rows of the call), the layout pf_gemm_split3 reads with
  * korder bit 1; kmajor == 0: row-major [rows][ld]. */
+/* pf_layernorm_split3: Refused (PF_ERR_ARG): null pointers; x off a 16-byte, y3 off an 8-byte, g / b off a 4-byte boundary; D not a multiple of 8 in [8,
+ * 2048]; x_ld / y_ld not multiples of 8 or below D; rows outside [1, 2^31); plane below (rows - 1) y_ld + D or not a multiple of 4; kmajor with D % 32
+ * or y_ld != D. */
 int pf_layernorm_split3(const float* x, int x_ld, void* y3, int y_ld, long plane, int kmajor, const float* g, const float* b, float eps,
                         long rows, int D, void* stream);
 /* LayerNorm as the fp16x2 input of pf_gemm_f16x2: y2 = two fp16 planes, chunk-major [2][D/32][rows][32] (plane = rows * D elements), holding
  * LN(x)[k] / 2^in_exp[k] as h + l (in_exp: int32 [D], packing.pack_conv_f16x2 of the consuming linear) */
+/* pf_layernorm_f16x2: Refused (PF_ERR_ARG): null pointers; x / y2 off a 16-byte, in_exp / g / b off a 4-byte boundary; D not a multiple of 32 in [32,
+ * 2048]; x_ld not a multiple of 8 or below D; rows outside [1, 2^31). */
 int pf_layernorm_f16x2(const float* x, int x_ld, void* y2, const int* in_exp, const float* g, const float* b, float eps, long rows, int D,
                        void* stream);
+/* pf_vit_attention_qkv_split3: Refused (PF_ERR_ARG): null pointers; qkv off a 16-byte, out3 off an 8-byte boundary; B, S, Hh not positive; B * Hh >
+ * 65535 (grid dimension y); plane below B S Hh 64 or not a multiple of 4. */
 int pf_vit_attention_qkv_split3(const void* qkv, void* out3, long plane, int kmajor, int B, int S, int Hh, void* stream);
 /* The same attention entirely in split precision: qkv3 = the QKV GEMM's output as three bf16 planes [3][B*S][3*Hh*64] (plane stride plane_in
  * elements), out3 = three bf16 planes [3][B*S][Hh*64] (plane_out); S^T = K.Q^T and O^T = V^T.P^T as six bf16 partial products each with float32
  * accumulation, float32 softmax with the probabilities split in registers (csrc/vit.hip vit_attention_split3_kernel; attention.py:53-60). */
+/* pf_vit_attention_split3: Refused (PF_ERR_ARG): null pointers; qkv3 off a 16-byte, out3 off an 8-byte boundary; B, S, Hh not positive; B * Hh > 65535;
+ * plane_in below B S Hh 192 or not a multiple of 8, plane_out below B S Hh 64 or not a multiple of 4; 2 plane_in + 65 Hh 192 >= 2^32 (32-bit tile
+ * offsets). */
 int pf_vit_attention_split3(const void* qkv3, long plane_in, void* out3, long plane_out, int kmajor, int B, int S, int Hh, void* stream);
 /* Version 2 of the same operator (csrc/attn_split3.hip; same operands): K / V tiles by LDS-DMA, V^T fragments by the transposing LDS read, 32 (or
  * 16) queries per wave.  queries_per_wave: 16, 32, or 0 = 32 when the launch fills the chip with 128-query blocks, else 16.  schedule: 1 = the
  * two-phase kernel (64-key tiles; bit-identical to pf_vit_attention_split3), 2 = the software-pipelined kernel (32-key blocks, QK / softmax / PV of
  * three consecutive blocks overlapped inside every wave; float32-rounding-identical), 0 = default (2).  Requires S * Hh * 384 bytes < 2^31 (32-bit
  * row offsets inside one image).  Replaces dinov2/layers/attention.py:53-60. */
+/* pf_vit_attention_split3_v2: Refused (PF_ERR_ARG): null pointers; qkv3 off a 16-byte, out3 off an 8-byte boundary; B, S, Hh not positive; the plane
+ * rules of pf_vit_attention_split3; S * Hh * 384 bytes >= 2^31; queries_per_wave other than 0 / 16 / 32; schedule outside 0 .. 2. */
 int pf_vit_attention_split3_v2(const void* qkv3, long plane_in, void* out3, long plane_out, int kmajor, int B, int S, int Hh, int queries_per_wave,
                                int schedule, void* stream);
 /* The same attention on TWO SCALED fp16 PLANES (three v_mfma_f32_32x32x16_f16 per product term instead of six bf16 ones; the pipelined kernel's
@@ -222,6 +293,8 @@ int pf_vit_attention_split3_v2(const void* qkv3, long plane_in, void* out3, long
  * input of the projection as a pf_gemm_f16x2 layer whose in_exp is ev.  With v_exp3 != NULL (int32 [Hh*64] on the device, ev) the output is
  * written as THREE bf16 planes of out itself, chunk-major [3][Hh*2][B*S][32] -- the input of the projection as a pf_gemm_split3 layer (korder bit 1).
  * Float32 softmax and accumulation.  Requires S * Hh * 384 bytes < 2^31. */
+/* pf_vit_attention_f16x2: Refused (PF_ERR_ARG): as pf_vit_attention_split3_v2 for qkv2 / out, B, S, Hh and the planes; a null qk_exp or one off a 4-byte
+ * boundary; v_exp3 off a 16-byte boundary. */
 int pf_vit_attention_f16x2(const void* qkv2, long plane_in, const int* qk_exp, void* out, long plane_out, const int* v_exp3, int B, int S, int Hh,
                            void* stream);
 /* BEiT attention with a per-head relative-position bias (the MiDaS DPT_BEiT_L_384 core that midas.py:189-316 wraps, loaded at midas.py:340;
@@ -229,6 +302,8 @@ int pf_vit_attention_f16x2(const void* qkv2, long plane_in, const int* qk_exp, v
  * pf_vit_attention_split3_v2 (the two-phase kernel, same MFMA arithmetic).  S = th * tw + 1 (cls first); tab [Hh][(2 th - 1)(2 tw - 1) + 3]
  * float32, the bias table already interpolated to the (th, tw) window AND multiplied by log2(e); idx: patch x patch (yi - yj + th - 1)(2 tw - 1)
  * + (xi - xj + tw - 1), cls row -> entry n - 3, cls column -> n - 2, cls x cls -> n - 1.  queries_per_wave 16, 32 or 0 (as v2).  S < 2^20. */
+/* pf_vit_attention_split3_rpb: Refused (PF_ERR_ARG): as pf_vit_attention_split3_v2 for the operands, planes and queries_per_wave; a null tab or one off
+ * a 4-byte boundary; th, tw not positive, S != th tw + 1, S >= 2^20; a table slice that does not fit 160 KiB of LDS. */
 int pf_vit_attention_split3_rpb(const void* qkv3, long plane_in, void* out3, long plane_out, int kmajor, int B, int S, int Hh, const float* tab,
                                 int th, int tw, int queries_per_wave, void* stream);
 /* The same BEiT attention in the bf16 mode (csrc/vit.hip, the bias form of the 32-queries-per-wave bf16 kernel behind pf_vit_attention; same
@@ -237,89 +312,135 @@ int pf_vit_attention_split3_rpb(const void* qkv3, long plane_in, void* out3, lon
  * above (interpolated, times log2(e)): the kernel forms q.k * log2(e) + tab[h][idx(i, j)] in float32 (the bias is never rounded to bf16) and runs
  * its online softmax on those base-2 logits.  Refused (PF_ERR_ARG): null pointers, S != th * tw + 1, tw < 4, S >= 2^20, Sp not a multiple of 64 or
  * < S, a table slice that does not fit the LDS.  pf_vit_attention is unchanged. */
+/* pf_vit_attention_rpb_bf16: Refused (PF_ERR_ARG): also q / k / vt off a 16-byte, out off an 8-byte, tab off a 4-byte boundary; B, Hh not positive; B *
+ * Hh > 65535.  The LDS opt-in is kept per device and raised under a lock. */
 int pf_vit_attention_rpb_bf16(const void* q, const void* k, const void* vt, void* out, int B, int S, int Sp, int Hh, const float* tab, int th, int tw,
                               void* stream);
 /* LDS bytes one block of that kernel reserves: the 32 KiB of K / V^T stages + the largest table slice a 128-query block stages ((y_hi - y_lo + th)
  * (2 tw - 1) + 3 entries, rounded to 16 bytes); -1 for a shape pf_vit_attention_rpb_bf16 refuses.  No launch, no GPU (host-side tests). */
+/* pf_vit_attention_rpb_bf16_lds_bytes: Answers -1 for th <= 0, tw < 4, S != th tw + 1 or S >= 2^20. */
 int pf_vit_attention_rpb_bf16_lds_bytes(int S, int th, int tw);
 /* float32 [rows][x_ld] -> three bf16 planes [3][rows][y_ld], plane stride `plane` elements (the split producers fuse into their stores) */
+/* pf_split3: Refused (PF_ERR_ARG): null pointers; x off a 16-byte, y off an 8-byte boundary; cols not a positive multiple of 4; x_ld / y_ld not
+ * multiples of 4 or below cols; rows <= 0; plane below (rows - 1) y_ld + cols or not a multiple of 4. */
 int pf_split3(const float* x, int x_ld, void* y, int y_ld, long plane, long rows, int cols, void* stream);
 
 /* ---- ViT encoder pieces ---------------------------------------------------------------------- */
 /* (x - mean)/std + 14x14/14 patch gather: NCHW float image -> im2col rows [B*th*tw][ld] (K order
  * ky,kx,c).  Replaces depth_anything.py:184-190 (Normalize) + the unfold implied by patch_embed.py:76 */
+/* pf_patch_im2col: Refused (PF_ERR_ARG): null pointers or ones off their element size; a dtype other than 0 / 1; B, H, W not positive; H, W not
+ * multiples of 14; ld < 588. */
 int pf_patch_im2col(const float* img, int B, int H, int W, void* out, int ld, int dtype, void* stream);
 /* (x - mean[c])/std[c] + patch x patch / patch gather: NCHW float image -> float32 im2col rows [B*(H/patch)*(W/patch)][ld] (K order ky,kx,c;
  * columns 3 patch^2 .. ld-1 zero).  Replaces midas.py:160-169 (PrepForMidas Normalize(0.5, 0.5)) + the unfold implied by the BEiT patch_embed.proj
  * 16x16/16 conv of the core loaded at midas.py:340.  pf_patch_im2col (14x14, ImageNet statistics) is unchanged. */
+/* pf_patch_im2col_norm: Refused (PF_ERR_ARG): null pointers or ones off their element size (mean3 / std3 are HOST arrays of three floats); B, H, W,
+ * patch not positive, patch > 1024; H, W not multiples of patch; ld < 3 patch^2; a std that is 0 or NaN. */
 int pf_patch_im2col_norm(const float* img, int B, int H, int W, int patch, const float* mean3, const float* std3, float* out, int ld, void* stream);
 /* readout 'project' operand rows (MiDaS utils ProjectReadout, the act_postprocess*.0 of the core loaded at midas.py:340): x [B*S][x_ld] float32
  * token rows (cls first) -> y[b*(S-1) + t] = [x[b*S + 1 + t][0:D] | x[b*S][0:D]] (y_ld >= 2 D).  D, x_ld, y_ld multiples of 4; 16-byte pointers. */
+/* pf_readout_concat: Refused (PF_ERR_ARG): null pointers or ones off a 16-byte boundary; B < 1, S < 2; D, x_ld, y_ld not positive multiples of 4; x_ld <
+ * D; y_ld < 2 D. */
 int pf_readout_concat(const float* x, int x_ld, int B, int S, int D, float* y, int y_ld, void* stream);
 /* The bf16 mode's forms of those two (csrc/beit_bf16.hip; same reference lines): pf_patch_im2col_norm_bf16 writes bf16 rows [..][ld] -- the float32
  * kernel's value rounded once to nearest even, padding columns zero; pf_readout_concat_bf16 copies bf16 token rows x [B*S][x_ld] into bf16 rows y
  * [B*(S-1)][y_ld] = [token | cls].  D, x_ld, y_ld multiples of 8 there; 16-byte pointers.  Refusals as the float32 forms (PF_ERR_ARG). */
+/* pf_patch_im2col_norm_bf16: Refused (PF_ERR_ARG): as pf_patch_im2col_norm. */
 int pf_patch_im2col_norm_bf16(const float* img, int B, int H, int W, int patch, const float* mean3, const float* std3, void* out, int ld, void* stream);
+/* pf_readout_concat_bf16: Refused (PF_ERR_ARG): as pf_readout_concat with multiples of 8. */
 int pf_readout_concat_bf16(const void* x, int x_ld, int B, int S, int D, void* y, int y_ld, void* stream);
 /* tokens[b,0,:] = cls + pos[0]; tokens[b,1+t,:] = emb[b*(S-1)+t,:] + pos[1+t]  (vision_transformer.py:222-223) */
+/* pf_assemble_tokens: Refused (PF_ERR_ARG): null pointers or ones off their element size; a dtype other than 0 / 1; B, S not positive (S = 1: the cls
+ * token alone, emb is not read); D not a positive multiple of 8. */
 int pf_assemble_tokens(const void* emb, void* tokens, const float* cls, const float* pos, int B, int S, int D, int dtype,
                        void* stream);
 /* LayerNorm over the last dim: y[r] = (x[r]-mu)/sqrt(var+eps)*g+b.  Rows are remapped so that the
  * final `norm` + cls drop of get_intermediate_layers (vision_transformer.py:309-312) is one pass:
  * out row (b, t) <- in row b*in_rows_per_batch + in_row_offset + t, t < out_rows_per_batch. */
+/* pf_layernorm: Refused (PF_ERR_ARG): null pointers; x / y off a 16-byte, g / b off a 4-byte boundary; a dtype other than 0 / 1; D not a multiple of 8
+ * in [8, 2048]; x_ld / y_ld not multiples of 8 or below D (output rows would overlap); batches, in_rows_per_batch, out_rows_per_batch not positive;
+ * in_row_offset < 0 or in_row_offset + out_rows_per_batch > in_rows_per_batch (a read past the batch); 2^31 rows or more. */
 int pf_layernorm(const void* x, int x_ld, void* y, int y_ld, const float* g, const float* b, float eps,
                  int batches, int in_rows_per_batch, int in_row_offset, int out_rows_per_batch, int D,
                  int dtype, void* stream);
 /* split the fused qkv rows [B*S][3*D] into per-head Q*scale [B,H,S,64], K [B,H,S,64], V^T [B,H,64,Sp] */
+/* pf_qkv_split: Refused (PF_ERR_ARG): null pointers or ones off a 16-byte boundary; a dtype other than 0 / 1; B, S, Hh not positive; Sp not a multiple
+ * of 64 or below S; B * Hh > 65535 (grid dimension y). */
 int pf_qkv_split(const void* qkv, int B, int S, int Hh, void* q, void* k, void* vt, int Sp, float scale,
                  int dtype, void* stream);
 /* softmax(q k^T) v per (batch, head), head_dim 64, flash-style on the matrix cores; out [B*S][D].
  * Replaces dinov2/layers/attention.py:53-59 (the materialised N x N scores). */
+/* pf_vit_attention: Refused (PF_ERR_ARG): as pf_qkv_split (out: 8 bytes for bf16). */
 int pf_vit_attention(const void* q, const void* k, const void* vt, void* out, int B, int S, int Sp, int Hh,
                      int dtype, void* stream);
 /* float32 attention straight from the QKV GEMM's rows [B*S][3][Hh][64] (no pf_qkv_split, no Q / K / V^T buffers): softmax(q k^T / 8) v
  * per head, head_dim 64, out [B*S][Hh*64].  Same reference lines as pf_vit_attention (dinov2/layers/attention.py:49-62); base-2 softmax
  * with the hardware exponential (relative error ~1e-7 per probability).  dtype must be PF_DTYPE_F32. */
+/* pf_vit_attention_qkv: Refused (PF_ERR_ARG): null pointers or ones off a 16-byte boundary; a dtype other than float32; B, S, Hh not positive; B * Hh >
+ * 65535. */
 int pf_vit_attention_qkv(const void* qkv, void* out, int B, int S, int Hh, int dtype, void* stream);
 
 /* ---- G2L (Swin window attention) -------------------------------------------------------------- */
 /* LayerNorm(norm1) -> zero pad to a multiple of 12 -> cyclic shift -> window partition
  * (swin_layers.py:223-244): x [B,H,W,C] tokens -> xw [B*nW*144][C] */
+/* pf_swin_ln_partition: Refused (PF_ERR_ARG): null pointers; x / xw off a 16-byte, g / b off a 4-byte boundary; a dtype other than 0 / 1; B, H, W not
+ * positive; C / 8 not a power of two in [1, 64]; x_ld not a multiple of 8 or below C; shift outside [0, 12); 2^31 padded tokens or more. */
 int pf_swin_ln_partition(const void* x, int x_ld, void* xw, const float* g, const float* b, float eps,
                          int B, int H, int W, int C, int shift, int dtype, void* stream);
 /* window attention with relative-position bias and shift mask (swin_layers.py:133-164,327-345);
  * qkv [B*nW*144][3C] -> out [B*nW*144][C]; bias_table [529][heads] float */
+/* pf_swin_window_attention: Refused (PF_ERR_ARG): null pointers; qkv / out off a 16-byte, bias_table off a 4-byte boundary; a dtype other than 0 / 1; B,
+ * Hp, Wp not positive, Hp / Wp not multiples of 12; C not a positive multiple of 8; heads outside [1, 65535] or not dividing C (heads = 0 used to divide
+ * by zero on the host); a head_dim C / heads outside {2, 4, 8, 16, 32}; shift outside [0, 12). */
 int pf_swin_window_attention(const void* qkv, void* out, const float* bias_table, int B, int Hp, int Wp,
                              int C, int heads, int shift, int dtype, void* stream);
 /* window reverse + un-shift + crop + residual (swin_layers.py:250-263): y = shortcut + proj[win(tok)] */
+/* pf_swin_unpartition_add: Refused (PF_ERR_ARG): null pointers or ones off a 16-byte boundary; a dtype other than 0 / 1; B, H, W not positive; C not a
+ * positive multiple of 8; s_ld / y_ld not multiples of 8 or below C; shift outside [0, 12). */
 int pf_swin_unpartition_add(const void* proj, const void* shortcut, int s_ld, void* y, int y_ld, int B, int H,
                             int W, int C, int shift, int dtype, void* stream);
 /* x[b,t,:] += pos[t,:]  (absolute_pos_embed, swin_layers.py:419-420); pos float [T][C] */
+/* pf_add_rowwise: Refused (PF_ERR_ARG): null pointers; x off a 16-byte, pos off a 4-byte boundary; a dtype other than 0 / 1; B, T not positive; C not a
+ * positive multiple of 8; x_ld not a multiple of 8 or below C. */
 int pf_add_rowwise(void* x, int x_ld, const float* pos, int B, int T, int C, int dtype, void* stream);
 
 /* ---- memory-bound image ops --------------------------------------------------------------------- */
 /* bilinear, align_corners=True (F.interpolate; used at dpt.py:126,154, blocks.py:147,
  * attractor.py:179,186, zoedepth_v1.py:204-214, guided_fusion_model.py:97,192).
  * y[b,oy,ox, 0..C) = (add ? add[...] : 0) + interp(x).  NHWC both sides. */
+/* pf_resize_bilinear: Refused (PF_ERR_ARG): null x / y; x, y, add off a 16-byte boundary; a dtype other than 0 / 1; B, H, W, OH, OW not positive; C not
+ * a positive multiple of 8; x_ld / y_ld (add_ld with add) not multiples of 8 or below C; 2^31 (batch, row) pairs or items of a row. */
 int pf_resize_bilinear(const void* x, int x_ld, int B, int H, int W, int C, void* y, int y_ld, int OH, int OW,
                        const void* add, int add_ld, int in_f32, int out_f32, int dtype, void* stream);
 /* nsrc (2 or 3) bilinear align_corners=True resizes of NHWC tensors xs[i] [B,Hs[i],Ws[i],Cs[i]] (pixel stride lds[i]) written to
  * consecutive channel ranges of y [B,OH,OW, sum Cs] (pixel stride y_ld): the Upv1 concat of guided_fusion_model.py:96-99
  * (cat[feat_enc_resized, up(temp), up(guide)]) in one launch.  All tensors in `dtype`.  The five arrays are HOST arrays. */
+/* pf_resize_concat: Refused (PF_ERR_ARG): null arrays, sources or y; a source or y off a 16-byte boundary; nsrc outside 2 .. 3; a dtype other than 0 /
+ * 1; per source the rules of pf_resize_bilinear; y_ld not a multiple of 8 or below the sum of the channels. */
 int pf_resize_concat(const void* const* xs, const int* lds, const int* Hs, const int* Ws, const int* Cs, int nsrc, int B,
                      void* y, int y_ld, int OH, int OW, int dtype, void* stream);
 /* planar float version for the image crops (depth_anything/transform.py:127-129 applied per tile,
  * baseline_pretrain.py:258-264): img [3][H][W] float -> out [P][3][oh][ow] float; boxes int [P][4]=(x0,y0,x1,y1) */
+/* pf_crop_resize_planar: Refused (PF_ERR_ARG): null pointers or ones off a 4-byte boundary; C, H, W, P, oh, ow not positive; 2^29 boxes or more.  (The
+ * boxes live on the device: they must lie inside the image.) */
 int pf_crop_resize_planar(const float* img, int C, int H, int W, const int* boxes, int P, float* out, int oh, int ow,
                           void* stream);
 /* torchvision.ops.roi_align(aligned=True, sampling_ratio=-1) (patchfusion.py:247,251;
  * guided_fusion_model.py:202). feat [Bf,H,W,C] NHWC; rois float [K][5] = (batch, x1,y1,x2,y2);
  * out [K,oh,ow,C] (ld y_ld).  in_f32/out_f32 select float storage for the depth map. */
+/* pf_roi_align: Refused (PF_ERR_ARG): null pointers; rois off a 4-byte boundary; a dtype other than 0 / 1; Bf, H, W, C, K, oh, ow not positive;
+ * spatial_scale not positive; C = 1 (planar) without in_f32 and out_f32 or with feat / y off a 4-byte boundary; C > 1 not a multiple of 8, f_ld / y_ld
+ * not multiples of 8 or below C, feat / y off a 16-byte boundary; K * oh >= 2^31.  The batch index of an RoI lives on the device: the kernels CLAMP it
+ * to [0, Bf) (NaN -> 0). */
 int pf_roi_align(const void* feat, int f_ld, int Bf, int H, int W, int C, const float* rois, int K, void* y,
                  int y_ld, int oh, int ow, float spatial_scale, int in_f32, int out_f32, int dtype, void* stream);
 /* nn.MaxPool2d(2) (guided_fusion_model.py:78) */
+/* pf_maxpool2: Refused (PF_ERR_ARG): null pointers or ones off a 16-byte boundary; a dtype other than 0 / 1; B not positive, H or W < 2 (odd sizes
+ * floor); C not a positive multiple of 8; x_ld / y_ld not multiples of 8 or below C. */
 int pf_maxpool2(const void* x, int x_ld, int B, int H, int W, int C, void* y, int y_ld, int dtype, void* stream);
 /* channel-slice copy y[..., 0..C) = x[..., 0..C) with optional dtype change */
+/* pf_copy_channels: Refused (PF_ERR_ARG): null pointers or ones off a 16-byte boundary; a dtype other than 0 / 1; npix <= 0; C not a positive multiple
+ * of 8; x_ld / y_ld not multiples of 8 or below C. */
 int pf_copy_channels(const void* x, int x_ld, void* y, int y_ld, long npix, int C, int in_f32, int out_f32,
                      int dtype, void* stream);
 /* The same four calls as PRODUCERS of an fp16x2 Winograd layer's range pass (pf_conv_winograd_f16x2_windowed_ex cmax_in): with cmax != NULL (float32
@@ -329,19 +450,28 @@ int pf_copy_channels(const void* x, int x_ld, void* y, int y_ld, long npix, int 
  * Unsigned maxima are order-free, so the vector equals pf_wino_absmax over the finished channels bit for bit; y is bit-identical with and without
  * cmax.  cmax == NULL: exactly the plain call. */
 /* n uint32 words at p = 0, one memset on `stream` (the maxima vector before its first producer) */
+/* pf_zero_u32: Refused (PF_ERR_ARG): a null p or one off a 4-byte boundary; n <= 0. */
 int pf_zero_u32(void* p, long n, void* stream);
+/* pf_resize_bilinear_ex: Refused (PF_ERR_ARG): as pf_resize_bilinear; cmax off a 4-byte boundary or given to a call that is not float32. */
 int pf_resize_bilinear_ex(const void* x, int x_ld, int B, int H, int W, int C, void* y, int y_ld, int OH, int OW,
                           const void* add, int add_ld, int in_f32, int out_f32, int dtype, void* cmax, void* stream);
+/* pf_resize_concat_ex: Refused (PF_ERR_ARG): as pf_resize_concat; cmax off a 4-byte boundary or given to a call that is not float32. */
 int pf_resize_concat_ex(const void* const* xs, const int* lds, const int* Hs, const int* Ws, const int* Cs, int nsrc, int B,
                         void* y, int y_ld, int OH, int OW, int dtype, void* cmax, void* stream);
+/* pf_roi_align_ex: Refused (PF_ERR_ARG): as pf_roi_align; cmax off a 4-byte boundary or given to a call that is not float32, to the planar C = 1 form or
+ * to C > 8192. */
 int pf_roi_align_ex(const void* feat, int f_ld, int Bf, int H, int W, int C, const float* rois, int K, void* y,
                     int y_ld, int oh, int ow, float spatial_scale, int in_f32, int out_f32, int dtype, void* cmax, void* stream);
+/* pf_copy_channels_ex: Refused (PF_ERR_ARG): as pf_copy_channels; cmax off a 4-byte boundary or given to a call that is not float32 or has C > 8192. */
 int pf_copy_channels_ex(const void* x, int x_ld, void* y, int y_ld, long npix, int C, int in_f32, int out_f32,
                         int dtype, void* cmax, void* stream);
 /* fusion-net input cat[coarse_depth_roi, fine_depth, rgb crop] (patchfusion.py:269) -> [B,h,w,8] (3 zero pad) */
+/* pf_pack_fusion_input: Refused (PF_ERR_ARG): null pointers; the planes off a 4-byte, y off a 16-byte boundary; a dtype other than 0 / 1; B, h, w not
+ * positive. */
 int pf_pack_fusion_input(const float* cdepth, const float* fdepth, const float* crops, void* y, int B, int h, int w,
                          int dtype, void* stream);
 /* NHWC (ld) <-> NCHW float converters for the module boundary */
+/* pf_nhwc_to_nchw_f32: Refused (PF_ERR_ARG): null pointers or ones off their element size; a dtype other than 0 / 1; B, H, W, C not positive; x_ld < C. */
 int pf_nhwc_to_nchw_f32(const void* x, int x_ld, float* y, int B, int H, int W, int C, int in_f32, int dtype, void* stream);
 
 /* ---- metric-bins head ----------------------------------------------------------------------------- */
@@ -352,18 +482,24 @@ int pf_nhwc_to_nchw_f32(const void* x, int x_ld, float* y, int B, int H, int W, 
  *   kind_sum 0: mean over the attractors, 1: sum;
  *   unnormed layer: A = softplus(mlp), a_stride 1, a_eps 0; bounded layer: A = relu(mlp) (2 n_attr channels), a_stride 2, a_eps 1e-3
  *   (:105-106 overwrites the normalised pair with A[:, :, 0]).  All float. */
+/* pf_attractor: Refused (PF_ERR_ARG): null pointers; A off a 4-byte, b_prev / out off a 16-byte boundary; n_bins not a positive multiple of 4; n_attr <
+ * 1, a_stride < 1, a_ld < (n_attr - 1) a_stride + 1; B, h, w, hp, wp not positive. */
 int pf_attractor(const float* A, int a_ld, int n_attr, int a_stride, float a_eps, int attractor_exp, int kind_sum,
                  const float* b_prev, int hp, int wp, float* out, int B, int h, int w, int n_bins, void* stream);
 /* Seed bin centres of the bounded variants: x [npix][x_ld] float = relu(mlp) (bounded) or softplus(mlp), out [npix][n_bins].
  *   bounded   (SeedBinRegressor, localbins_layers.py:52-68): Bn = x + 1e-3; widths = (max - min) Bn / sum(Bn); edges = cumsum([min, widths]);
  *             centre_k = (edge_k + edge_k+1) / 2
  *   normalize (zoedepth_v1.py:178-182, 'normed' and 'hybrid2'): centre -> (centre - min) / (max - min) */
+/* pf_seed_bin_centers: Refused (PF_ERR_ARG): null pointers or ones off a 4-byte boundary; npix <= 0; n_bins < 1; x_ld < n_bins. */
 int pf_seed_bin_centers(const float* x, int x_ld, float* out, long npix, int n_bins, float min_depth, float max_depth, int bounded,
                         int normalize, void* stream);
 /* AttractorLayer tail (attractor.py:132-135): out = clip(sort_k((max - min) * b + min), min, max) per pixel; n_bins <= 64 */
+/* pf_bounded_bin_centers: Refused (PF_ERR_ARG): null pointers or ones off a 4-byte boundary; npix <= 0; n_bins outside [1, 64]. */
 int pf_bounded_bin_centers(const float* b, float* out, long npix, int n_bins, float min_depth, float max_depth, void* stream);
 /* ConditionalLogBinomial tail + expectation (dist_layers.py:29-33,51-69,108-121, zoedepth_v1.py:215-219):
  * pt [B,h,w,4] float = softplus(mlp) ; centers [B,hc,wc,n_bins] float ; depth [B,h,w] float */
+/* pf_logbinom_depth: Refused (PF_ERR_ARG): null pointers; pt / depth off a 4-byte, centers off a 16-byte boundary; n_bins not a multiple of 4 in [4,
+ * 256]; pt_ld < 4; B, h, w, hc, wc not positive. */
 int pf_logbinom_depth(const float* pt, int pt_ld, const float* centers, int hc, int wc, float* depth, int B, int h,
                       int w, int n_bins, float min_temp, float max_temp, void* stream);
 /* The whole full-resolution tail of a metric-bins head in one launch (float32): cat[last(32), up(b_embedding)(128), rel?] -> Conv1x1(80) +
@@ -371,22 +507,32 @@ int pf_logbinom_depth(const float* pt, int pt_ld, const float* centers, int hc, 
  * clb: the CLB buffer [B,H,W,clb_ld] whose channels [0,32) hold `last` and (nq == 11) [rel_off, rel_off+8) the relative depth; emb: the
  * low-resolution embedding [B,he,we,128]; w0f / b0 / w2 / b2: packing.bins_tail_weights; centers [B,hc,wc,64]; depth [B,H,W].
  * Replaces pf_resize_bilinear (embedding into the CLB buffer) + two pf_conv + pf_logbinom_depth. */
+/* pf_bins_tail: Refused (PF_ERR_ARG): null pointers; clb / emb / w0f / centers off a 16-byte, b0 / w2 / b2 / depth off a 4-byte boundary; clb_ld not a
+ * multiple of 4 or below 32; nq other than 10 / 11; with nq = 11 a rel_off that is negative, not a multiple of 4 or with rel_off + 8 > clb_ld; B, H, W,
+ * he, we, hc, wc not positive. */
 int pf_bins_tail(const float* clb, int clb_ld, int rel_off, const float* emb, int he, int we, const float* w0f, const float* b0,
                  const float* w2, const float* b2, const float* centers, int hc, int wc, float* depth, int B, int H, int W, int nq,
                  float min_temp, float max_temp, void* stream);
 
 /* ---- stitching (estimator/models/utils.py:21-36, baseline_pretrain.py:310-329,205-216) ------------ */
 /* init pass: pred[y0+i,x0+j] = depth*mask ; count[...] = mask  (P tiles) */
+/* pf_stitch_init: Refused (PF_ERR_ARG): null pointers or ones off a 4-byte boundary; MH, MW, P, ph, pw not positive.  (yx lives on the device: tiles are
+ * clipped at every edge of the map.) */
 int pf_stitch_init(float* pred, float* count, int MH, int MW, const float* depth, const float* mask, const int* yx,
                    int P, int ph, int pw, void* stream);
+/* pf_stitch_finish_init: Refused (PF_ERR_ARG): null pointers or ones off a 4-byte boundary; n <= 0. */
 int pf_stitch_finish_init(float* avg, const float* pred, const float* count, long n, void* stream);
 /* RunningAverageMap.update restricted to the tile's footprint, tiles applied in order.
  * depth tile is [dh][dw]; when (dh,dw) != (ph,pw) it is nearest-resized (F.interpolate default,
  * baseline_pretrain.py:203) on the fly. */
+/* pf_stitch_update: Refused (PF_ERR_ARG): null pointers or ones off a 4-byte boundary; MH, MW, dh, dw, ph, pw not positive; a paste window that starts
+ * outside the map (y0 or x0 negative, y0 >= MH, x0 >= MW) -- it is clipped at the far edges only. */
 int pf_stitch_update(float* avg, float* count, int MH, int MW, const float* depth, int dh, int dw, const float* mask,
                      int y0, int x0, int ph, int pw, void* stream);
 /* RunningAverageMap.resize: avg nearest, count bilinear align_corners */
+/* pf_resize_nearest_f32: Refused (PF_ERR_ARG): null pointers or ones off a 4-byte boundary; H, W, OH, OW not positive. */
 int pf_resize_nearest_f32(const float* x, int H, int W, float* y, int OH, int OW, void* stream);
+/* pf_resize_bilinear_f32: Refused (PF_ERR_ARG): as pf_resize_nearest_f32. */
 int pf_resize_bilinear_f32(const float* x, int H, int W, float* y, int OH, int OW, void* stream);
 
 /* ==== input / output side of the path: HBM-bound byte/float streaming ==== */

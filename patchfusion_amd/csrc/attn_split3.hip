@@ -27,8 +27,10 @@
 // accumulator quads); V^T fragment (16 d): lane (r = d, g) needs the same eight keys of column 16 fd + r = two tr reads of keys 32 kk + 16 a + 4 g ..+3.
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
+#include "pf_args.h"
 
 #include <atomic>
+#include <mutex>
 #include <cstdlib>
 #include <type_traits>
 
@@ -1245,14 +1247,27 @@ constexpr int V2_LDS = 3 * KS_BYTES;
 
 }  // namespace
 
+// The plane operands of the three entry points: refused are B, S, Hh that are not positive, planes that do not hold their rows or are not multiples of
+// 8 (in: 16-byte loads) / 4 (out: 8-byte stores) elements, S * Hh * 384 bytes >= 2^31 (32-bit byte offsets inside one image's rows) and more than
+// 2^31 - 1 blocks.
+static const char* attn_planes(int B, int S, int Hh, long plane_in, long plane_out) {
+  if (B <= 0 || S <= 0 || Hh <= 0) return "B, S, Hh must be positive";
+  if (plane_in < (long)B * S * Hh * 192 || plane_out < (long)B * S * Hh * 64 || plane_in % 8 || plane_out % 4)
+    return "planes must hold their rows (plane_in a multiple of 8, plane_out of 4)";
+  if ((long)S * Hh * 192 * 2 >= (1L << 31)) return "S * Hh * 384 bytes must be below 2^31";
+  if (((long)S + 63) / 64 * B * Hh >= (1L << 31)) return "too many blocks";
+  return nullptr;
+}
+
 // C entry: see include/pf_hip.h.  schedule = 1: the two-phase kernel (queries_per_wave = 16 or 32, 0 = 32 when the grid of 128-query blocks fills the chip,
 // else 16), 2: the pipelined kernel (always 32 queries per wave), 0 = default (pipelined).
 extern "C" int pf_vit_attention_split3_v2(const void* qkv3, long plane_in, void* out3, long plane_out, int kmajor, int B, int S, int Hh,
                                           int queries_per_wave, int schedule, void* stream) {
-  if (!qkv3 || !out3 || B <= 0 || S <= 0 || Hh <= 0 || plane_in < (long)B * S * Hh * 192 || plane_out < (long)B * S * Hh * 64) return PF_ERR_ARG;
-  if ((long)S * Hh * 192 * 2 >= (1L << 31)) return PF_ERR_ARG;                           // 32-bit byte offsets inside one image's rows
-  if (queries_per_wave != 0 && queries_per_wave != 16 && queries_per_wave != 32) return PF_ERR_ARG;
-  if (schedule < 0 || schedule > 2) return PF_ERR_ARG;
+  if (!qkv3 || !out3) return pf_refuse("pf_vit_attention_split3_v2", "null tensor");
+  if (pf_misaligned(qkv3, 16) || pf_misaligned(out3, 8)) return pf_refuse("pf_vit_attention_split3_v2", "misaligned tensor");
+  if (const char* e = attn_planes(B, S, Hh, plane_in, plane_out)) return pf_refuse("pf_vit_attention_split3_v2", e);
+  if (queries_per_wave != 0 && queries_per_wave != 16 && queries_per_wave != 32) return pf_refuse("pf_vit_attention_split3_v2", "queries_per_wave must be 0, 16 or 32");
+  if (schedule < 0 || schedule > 2) return pf_refuse("pf_vit_attention_split3_v2", "schedule must be 0, 1 or 2");
   const float qscale = 0.125f * 1.4426950408889634f;        // head_dim^-1/2 (attention.py:55) times log2(e): base-2 softmax
   int dbg = 0, lds2 = V2_LDS, ldsp = PIPE_LDS;
 #ifdef PF_ATTN_DBG
@@ -1299,8 +1314,9 @@ extern "C" int pf_vit_attention_split3_v2(const void* qkv3, long plane_in, void*
 extern "C" int pf_vit_attention_f16x2(const void* qkv2, long plane_in, const int* qk_exp, void* out, long plane_out, const int* v_exp3, int B, int S, int Hh,
                                       void* stream) {
   void* out2 = out;
-  if (!qkv2 || !qk_exp || !out2 || B <= 0 || S <= 0 || Hh <= 0 || plane_in < (long)B * S * Hh * 192 || plane_out < (long)B * S * Hh * 64) return PF_ERR_ARG;
-  if ((long)S * Hh * 192 * 2 >= (1L << 31)) return PF_ERR_ARG;                           // 32-bit byte offsets inside one image's rows
+  if (!qkv2 || !qk_exp || !out2) return pf_refuse("pf_vit_attention_f16x2", "null tensor");
+  if (pf_misaligned(qkv2, 16) || pf_misaligned(out2, 8) || pf_misaligned(qk_exp, 4) || pf_misaligned(v_exp3, 16)) return pf_refuse("pf_vit_attention_f16x2", "misaligned tensor");
+  if (const char* e = attn_planes(B, S, Hh, plane_in, plane_out)) return pf_refuse("pf_vit_attention_f16x2", e);
   static std::atomic<unsigned long long> attr_done{0};
   int dev = 0;
   hipGetDevice(&dev);
@@ -1320,11 +1336,12 @@ extern "C" int pf_vit_attention_f16x2(const void* qkv2, long plane_in, const int
 // C entry: see include/pf_hip.h.  The two-phase kernel with the relative-position bias (RPB = true above).
 extern "C" int pf_vit_attention_split3_rpb(const void* qkv3, long plane_in, void* out3, long plane_out, int kmajor, int B, int S, int Hh,
                                            const float* tab, int th, int tw, int queries_per_wave, void* stream) {
-  if (!qkv3 || !out3 || !tab || B <= 0 || Hh <= 0 || th <= 0 || tw <= 0 || plane_in < (long)B * S * Hh * 192 || plane_out < (long)B * S * Hh * 64)
-    return PF_ERR_ARG;
-  if ((long)th * tw + 1 != S || S >= (1 << 20)) return PF_ERR_ARG;               // one cls token + the th x tw grid; the key-row division is exact below 2^20
-  if ((long)S * Hh * 192 * 2 >= (1L << 31)) return PF_ERR_ARG;
-  if (queries_per_wave != 0 && queries_per_wave != 16 && queries_per_wave != 32) return PF_ERR_ARG;
+  if (!qkv3 || !out3 || !tab) return pf_refuse("pf_vit_attention_split3_rpb", "null tensor");
+  if (pf_misaligned(qkv3, 16) || pf_misaligned(out3, 8) || pf_misaligned(tab, 4)) return pf_refuse("pf_vit_attention_split3_rpb", "misaligned tensor");
+  if (th <= 0 || tw <= 0 || (long)th * tw + 1 != S || S >= (1 << 20))              // one cls token + the th x tw grid; the key-row division is exact below 2^20
+    return pf_refuse("pf_vit_attention_split3_rpb", "S must be th * tw + 1 < 2^20");
+  if (const char* e = attn_planes(B, S, Hh, plane_in, plane_out)) return pf_refuse("pf_vit_attention_split3_rpb", e);
+  if (queries_per_wave != 0 && queries_per_wave != 16 && queries_per_wave != 32) return pf_refuse("pf_vit_attention_split3_rpb", "queries_per_wave must be 0, 16 or 32");
   int qw = queries_per_wave;
   if (qw == 0) qw = (long)((S + 127) / 128) * B * Hh >= 512 ? 32 : 16;
   const int QB = 4 * qw, n_qb = (S + QB - 1) / QB, wq = 2 * tw - 1;
@@ -1335,12 +1352,23 @@ extern "C" int pf_vit_attention_split3_rpb(const void* qkv3, long plane_in, void
     rows = rows > y_hi - y_lo + th ? rows : y_hi - y_lo + th;
   }
   const int lds = 3 * KS_BYTES + ((rows * wq + 3) * 4 + 15) / 16 * 16;
-  if (lds > 160 * 1024) return PF_ERR_ARG;
+  if (lds > 160 * 1024) return pf_refuse("pf_vit_attention_split3_rpb", "the table slice does not fit the LDS");
   const void* k = qw == 32 ? reinterpret_cast<const void*>(vit_attention_split3_rpb_kernel<2>) : reinterpret_cast<const void*>(vit_attention_split3_rpb_kernel<1>);
-  static int attr_lds[2] = {0, 0};
-  if (attr_lds[qw == 32] < lds) {
-    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return PF_ERR_LAUNCH;
-    attr_lds[qw == 32] = lds;
+  // (the attribute belongs to a device and only ever grows: the size set so far per device and kernel, raised under a lock)
+  static std::mutex attr_mu;
+  static std::atomic<int> attr_lds[64][2];                    // (the other launchers opt in to ONE fixed size and keep a bit per device; this size grows with the
+  // window -- a bit cannot say "large enough", so the largest size set so far is kept per device, dev & 63 like those bitmasks)
+  {
+    int dev = 0;
+    hipGetDevice(&dev);
+    std::atomic<int>& have = attr_lds[dev & 63][qw == 32];
+    if (have.load(std::memory_order_acquire) < lds) {         // the lock is taken only by a call that has to raise the size
+      std::lock_guard<std::mutex> hold(attr_mu);
+      if (have.load(std::memory_order_relaxed) < lds) {
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return PF_ERR_LAUNCH;
+        have.store(lds, std::memory_order_release);
+      }
+    }
   }
   const float qscale = 0.125f * 1.4426950408889634f;        // head_dim^-1/2 times log2(e); the table is pre-multiplied by log2(e)
   const long kmaj_rows = kmajor ? (long)B * S : 0L;

@@ -3,6 +3,7 @@
 // (MiDaS PrepForMidas Normalize(0.5, 0.5), midas.py:160-169, + BEiT patch_embed.proj) and the readout-'project' operand rows [token | cls].
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
+#include "pf_args.h"
 
 namespace {
 
@@ -51,10 +52,13 @@ inline int grid_for(long n, int block) {
 
 extern "C" int pf_patch_im2col_norm(const float* img, int B, int H, int W, int patch, const float* mean3, const float* std3, float* out, int ld,
                                     void* stream) {
-  if (!img || !out || !mean3 || !std3 || B <= 0 || patch <= 0 || H % patch || W % patch || ld < 3 * patch * patch) return PF_ERR_ARG;
+  if (!img || !out || !mean3 || !std3) return pf_refuse("pf_patch_im2col_norm", "null pointer");
+  if (pf_misaligned(img, 4) || pf_misaligned(out, 4) || pf_misaligned(mean3, 4) || pf_misaligned(std3, 4)) return pf_refuse("pf_patch_im2col_norm", "misaligned pointer");
+  if (B <= 0 || H <= 0 || W <= 0 || patch <= 0 || patch > 1024 || H % patch || W % patch || ld < 3 * patch * patch)
+    return pf_refuse("pf_patch_im2col_norm", "B, H, W must be positive, H and W multiples of patch <= 1024, ld >= 3 patch^2");
   Norm3 n;
   for (int c = 0; c < 3; ++c) {
-    if (!(std3[c] != 0.f)) return PF_ERR_ARG;
+    if (!(std3[c] != 0.f) || std3[c] != std3[c]) return pf_refuse("pf_patch_im2col_norm", "std must not be zero (or NaN)");
     n.mean[c] = mean3[c];
     n.stdv[c] = std3[c];
   }
@@ -65,8 +69,10 @@ extern "C" int pf_patch_im2col_norm(const float* img, int B, int H, int W, int p
 }
 
 extern "C" int pf_readout_concat(const float* x, int x_ld, int B, int S, int D, float* y, int y_ld, void* stream) {
-  if (!x || !y || B <= 0 || S < 2 || D <= 0 || D % 4 || x_ld % 4 || y_ld % 4 || x_ld < D || y_ld < 2 * D) return PF_ERR_ARG;
-  if (((uintptr_t)x | (uintptr_t)y) & 15) return PF_ERR_ARG;
+  if (!x || !y) return pf_refuse("pf_readout_concat", "null tensor");
+  if (B <= 0 || S < 2 || D <= 0 || D % 4 || x_ld % 4 || y_ld % 4 || x_ld < D || y_ld < 2L * D)
+    return pf_refuse("pf_readout_concat", "B >= 1, S >= 2, D, x_ld, y_ld multiples of 4, x_ld >= D, y_ld >= 2 D");
+  if (pf_misaligned(x, 16) || pf_misaligned(y, 16)) return pf_refuse("pf_readout_concat", "misaligned tensor");
   const long total = (long)B * (S - 1) * (D / 2);
   hipLaunchKernelGGL(readout_concat_kernel, dim3(grid_for(total, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, x_ld, B, S, D, y, y_ld);
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;

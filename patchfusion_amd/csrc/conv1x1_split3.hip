@@ -32,6 +32,7 @@
 #include <cstdlib>
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
+#include "pf_args.h"
 
 namespace {
 
@@ -274,30 +275,33 @@ __global__ __launch_bounds__(4 * BM, 2) void conv1x1_split3_kernel(const pf_conv
 
 // declared in include/pf_hip.h
 extern "C" int pf_conv1x1_split3(const pf_conv_params* p, const void* w3, int w3_rows, void* stream) {
-  if (!p || !p->x || !p->y || !w3) return PF_ERR_ARG;
+  if (!p || !p->x || !p->y || !w3) return pf_refuse("pf_conv1x1_split3", "null tensor");
 #ifdef PF_C1_DBG
   pf_conv_params pd = *p;
   if (const char* s = getenv("PF_C1_DBG")) pd.pad = atoi(s);
   p = &pd;
-  if (p->dtype != PF_DTYPE_F32 || p->KH != 1 || p->KW != 1 || p->stride != 1 || p->shuffle > 1) return PF_ERR_ARG;
+  if (p->dtype != PF_DTYPE_F32 || p->KH != 1 || p->KW != 1 || p->stride != 1 || p->shuffle > 1) return pf_refuse("pf_conv1x1_split3", "argument outside the envelope (include/pf_hip.h)");
 #else
-  if (p->dtype != PF_DTYPE_F32 || p->KH != 1 || p->KW != 1 || p->stride != 1 || p->pad != 0 || p->shuffle > 1) return PF_ERR_ARG;
+  if (p->dtype != PF_DTYPE_F32) return pf_refuse("pf_conv1x1_split3", "float32 only");
+  if (const char* e = pf_linear_envelope(*p)) return pf_refuse("pf_conv1x1_split3", e);
+  if (p->batch > 1) return pf_refuse("pf_conv1x1_split3", "no batch");
 #endif
-  if (p->Cin <= 0 || p->Cin % 32 || p->x_ld % 4 || p->x_ld < p->Cin) return PF_ERR_ARG;
-  if (p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || w3_rows < p->Cout || w3_rows % 16) return PF_ERR_ARG;
-  if ((p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) return PF_ERR_ARG;
+  if (p->y_ld < p->Cout || (p->res && p->res_ld < p->Cout) || (p->res2 && p->res2_ld < p->Cout)) return pf_refuse("pf_conv1x1_split3", "y_ld / residual ld below Cout");
+  if (p->Cin <= 0 || p->Cin % 32 || p->x_ld % 4 || p->x_ld < p->Cin) return pf_refuse("pf_conv1x1_split3", "argument outside the envelope (include/pf_hip.h)");
+  if (p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || w3_rows < p->Cout || w3_rows % 16) return pf_refuse("pf_conv1x1_split3", "argument outside the envelope (include/pf_hip.h)");
+  if ((p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) return pf_refuse("pf_conv1x1_split3", "argument outside the envelope (include/pf_hip.h)");
   const long M = (long)p->B * p->OH * p->OW;
-  if (M <= 0 || M >= (1L << 31) || (long)w3_rows * 64 >= (1L << 31)) return PF_ERR_ARG;
+  if (M <= 0 || M >= (1L << 31) || (long)w3_rows * 64 >= (1L << 31)) return pf_refuse("pf_conv1x1_split3", "argument outside the envelope (include/pf_hip.h)");
   // float4 loads / stores: x, y and w3 through the loaders and the store, bias and scale in registers, res and res2 in the epilogue
   if ((reinterpret_cast<size_t>(p->x) | reinterpret_cast<size_t>(p->y) | reinterpret_cast<size_t>(w3) | reinterpret_cast<size_t>(p->res) |
-       reinterpret_cast<size_t>(p->res2) | reinterpret_cast<size_t>(p->bias) | reinterpret_cast<size_t>(p->scale)) & 15) return PF_ERR_ARG;
+       reinterpret_cast<size_t>(p->res2) | reinterpret_cast<size_t>(p->bias) | reinterpret_cast<size_t>(p->scale)) & 15) return pf_refuse("pf_conv1x1_split3", "argument outside the envelope (include/pf_hip.h)");
   // PF_C1_BM = 64 | 128 forces a token tile (A/B, tests); default 64 (two blocks per CU).  PF_C1_PERSIST=0: one tile per block (A/B, tests).
   static const int force = [] { const char* e = getenv("PF_C1_BM"); return e ? atoi(e) : 0; }();
   static const bool persist = [] { const char* e = getenv("PF_C1_PERSIST"); return !(e && e[0] == '0'); }();
   static const int cus = [] { int d = 0, n = 0; hipGetDevice(&d); hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
   const int bm = force == 128 ? 128 : 64;
   const int mt = (int)((M + bm - 1) / bm), nt = (p->Cout + BN - 1) / BN;
-  if ((long)mt * nt >= (1L << 31)) return PF_ERR_ARG;
+  if ((long)mt * nt >= (1L << 31)) return pf_refuse("pf_conv1x1_split3", "argument outside the envelope (include/pf_hip.h)");
   // the grid: nslots token-tile slots per channel tile; persistent = as many blocks as are resident at once (two per CU at BM = 64, one at 128)
   int nslots = mt;
   if (persist) {

@@ -28,6 +28,7 @@
 #include <type_traits>
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
+#include "pf_args.h"
 
 namespace {
 

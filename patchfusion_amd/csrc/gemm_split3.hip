@@ -29,6 +29,7 @@
 #include <type_traits>
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
+#include "pf_args.h"
 
 namespace {
 
@@ -1385,15 +1386,21 @@ extern "C" int pf_gemm_split3(const pf_conv_params* p, void* stream) { return pf
 // for kernels of other streams -- the HBM-bound Winograd transforms of the other tile batch (csrc/winograd.hip run_split3).  0 = every CU.
 extern "C" int pf_gemm_split3_ex(const pf_conv_params* p, int grid_cap, void* stream) {
   const char* e = nullptr;
-  if (!p || !p->x || !p->w || !p->y) return PF_ERR_ARG;
+  if (!p || !p->x || !p->w || !p->y) return pf_refuse("pf_gemm_split3", "null tensor");
 #ifdef PF_S3_DBG
   pf_conv_params pd = *p;
   if (const char* s = getenv("PF_S3_DBG")) pd.pad = atoi(s);
   p = &pd;
   if (p->KH != 1 || p->KW != 1 || p->stride != 1 || p->shuffle > 1) e = "1x1 / linear layers only";
 #else
-  if (p->KH != 1 || p->KW != 1 || p->stride != 1 || p->pad != 0 || p->shuffle > 1) e = "1x1 / linear layers only";
+  if ((e = pf_linear_envelope(*p)) != nullptr) {}
 #endif
+  else if (pf_misaligned(p->x, 16) || pf_misaligned(p->w, 16) || pf_misaligned(p->y, (p->out_f32 || (p->korder & 8)) ? 16 : 8) || pf_misaligned(p->bias, 16) ||
+           pf_misaligned(p->scale, 16) || pf_misaligned(p->res, 16) || pf_misaligned(p->res2, 16))
+    e = "misaligned tensor (16 bytes; 8 for plane outputs)";
+  else if (p->y_ld < p->Cout || (p->res && p->res_ld < p->Cout) || (p->res2 && p->res2_ld < p->Cout)) e = "y_ld / residual ld below Cout";
+  else if (p->x_bstride % 8 || p->w_bstride % 8 || (!p->out_f32 && p->y_bstride % ((p->korder & 8) ? 8 : 4)))
+    e = "plane strides must keep the planes aligned (x, w: 8 elements, y: 4, chunk-major y: 8)";
   else if (p->Cin <= 0 || p->Cin % 32 || p->Kpad < p->Cin || p->Kpad % 32 || p->x_ld % 8 || p->x_ld < p->Cin) e = "K must be a multiple of 32, x_ld of 8";
   else if (p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || p->w_rows < p->Cout) e = "Cout / y_ld must be multiples of 4";
   else if ((p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) e = "residual ld must be a multiple of 4";
@@ -1408,7 +1415,7 @@ extern "C" int pf_gemm_split3_ex(const pf_conv_params* p, int grid_cap, void* st
 #else
   else if (p->batch > 1 && (!p->out_f32 || p->bias || p->scale || p->res || p->res2 || p->batch > 65535)) e = "batched planes: float32 output, no epilogue";
 #endif
-  if (e) return PF_ERR_ARG;
+  if (e) return pf_refuse("pf_gemm_split3", e);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   switch (split3_route(*p, cu_count())) {
     case PF_S3_ROUTE_TILE64: return launch<64, 128, 2, 2, 2>(*p, st);
@@ -1431,14 +1438,17 @@ extern "C" int pf_gemm_split3_ex(const pf_conv_params* p, int grid_cap, void* st
 // fp16x2 batched product of the transform points (csrc/wino_f16x2.hip): x = V planes [2][batch][Cin/32][M][32] fp16 and w = U' planes
 // [2][batch][Cin/32][w_rows][32] fp16 (both chunk-major, korder = 6), y = float32 [batch][M][y_ld] = ldexp(sum_k w.x, col_exp[z][n]).
 extern "C" int pf_gemm_f16x2_points(const pf_conv_params* p, const int* col_exp, int grid_cap, void* stream) {
-  if (!p || !p->x || !p->w || !p->y || !col_exp) return PF_ERR_ARG;
+  if (!p || !p->x || !p->w || !p->y || !col_exp) return pf_refuse("pf_gemm_f16x2_points", "null tensor");
+  if (const char* e = pf_linear_envelope(*p)) return pf_refuse("pf_gemm_f16x2_points", e);
+  if (pf_misaligned(p->x, 16) || pf_misaligned(p->w, 16) || pf_misaligned(p->y, 16) || pf_misaligned(col_exp, 16)) return pf_refuse("pf_gemm_f16x2_points", "misaligned tensor");
+  if (p->y_ld < p->Cout || p->x_bstride % 8 || p->w_bstride % 8 || (p->batch > 1 && p->y_bstride % 4)) return pf_refuse("pf_gemm_f16x2_points", "y_ld below Cout or misaligning plane strides");
   const long M = (long)p->B * p->OH * p->OW;
-  if (p->KH != 1 || p->KW != 1 || p->stride != 1 || p->pad != 0 || p->shuffle > 1 || p->korder != 6 || !p->out_f32) return PF_ERR_ARG;
+  if (p->korder != 6 || !p->out_f32) return pf_refuse("pf_gemm_f16x2_points", "korder must be 6, the output float32");
   if (p->Cin <= 0 || p->Cin % 32 || p->x_ld != p->Cin || p->Kpad != p->Cin || p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || p->w_rows < p->Cout ||
       p->w_rows % 4)
-    return PF_ERR_ARG;
-  if (M <= 0 || M * 64 >= (1L << 31) || (long)p->w_rows * 64 >= (1L << 31) || p->x_bstride <= 0 || p->w_bstride <= 0) return PF_ERR_ARG;
-  if (p->bias || p->scale || p->res || p->res2 || p->act != PF_ACT_NONE || p->batch > 65535) return PF_ERR_ARG;
+    return pf_refuse("pf_gemm_f16x2_points", "argument outside the envelope (include/pf_hip.h)");
+  if (M <= 0 || M * 64 >= (1L << 31) || (long)p->w_rows * 64 >= (1L << 31) || p->x_bstride <= 0 || p->w_bstride <= 0) return pf_refuse("pf_gemm_f16x2_points", "argument outside the envelope (include/pf_hip.h)");
+  if (p->bias || p->scale || p->res || p->res2 || p->act != PF_ACT_NONE || p->batch > 65535) return pf_refuse("pf_gemm_f16x2_points", "argument outside the envelope (include/pf_hip.h)");
   pf_conv_params q = *p;
   q.scale = reinterpret_cast<const float*>(col_exp);     // (int32 exponents; the kernel's F16 epilogue reads them as such)
   return launch_persist192_f16(q, reinterpret_cast<hipStream_t>(stream), grid_cap);
@@ -1446,19 +1456,25 @@ extern "C" int pf_gemm_f16x2_points(const pf_conv_params* p, const int* col_exp,
 
 // fp16x2 linear layer (include/pf_hip.h pf_gemm_f16x2; the ViT block linears, packing.pack_conv_f16x2)
 extern "C" int pf_gemm_f16x2(const pf_conv_params* p, void* stream) {
-  if (!p || !p->x || !p->w || !p->y || !p->col_exp) return PF_ERR_ARG;
+  if (!p || !p->x || !p->w || !p->y || !p->col_exp) return pf_refuse("pf_gemm_f16x2", "null tensor");
+  if (const char* e = pf_linear_envelope(*p)) return pf_refuse("pf_gemm_f16x2", e);
+  if (pf_misaligned(p->x, 16) || pf_misaligned(p->w, 16) || pf_misaligned(p->y, (p->out_f32 || (p->korder & 16)) ? 16 : 8) || pf_misaligned(p->bias, 16) ||
+      pf_misaligned(p->scale, 16) || pf_misaligned(p->res, 16) || pf_misaligned(p->res2, 16) || pf_misaligned(p->col_exp, 16) || pf_misaligned(p->out_exp, 16))
+    return pf_refuse("pf_gemm_f16x2", "misaligned tensor (16 bytes; 8 for plane outputs)");
+  if (p->y_ld < p->Cout || (p->res && p->res_ld < p->Cout) || (p->res2 && p->res2_ld < p->Cout)) return pf_refuse("pf_gemm_f16x2", "y_ld / residual ld below Cout");
+  if (p->x_bstride % 8 || p->w_bstride % 8 || (!p->out_f32 && p->y_bstride % ((p->korder & 16) ? 8 : 4))) return pf_refuse("pf_gemm_f16x2", "plane strides must keep the planes aligned");
   const long M = (long)p->B * p->OH * p->OW;
-  if (p->KH != 1 || p->KW != 1 || p->stride != 1 || p->pad != 0 || p->shuffle > 1 || p->batch > 1 || (p->korder & ~48) != 6 || (p->korder & 48) == 48)
-    return PF_ERR_ARG;
+  if (p->batch > 1 || (p->korder & ~48) != 6 || (p->korder & 48) == 48)
+    return pf_refuse("pf_gemm_f16x2", "no batch; korder must be 6 with at most one of the bits 16 / 32");
   if (p->Cin <= 0 || p->Cin % 32 || p->x_ld != p->Cin || p->Kpad != p->Cin || p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || p->w_rows < p->Cout ||
       p->w_rows % 4)
-    return PF_ERR_ARG;
-  if (M <= 0 || M * 64 >= (1L << 31) || (long)p->w_rows * 64 >= (1L << 31) || p->x_bstride <= 0 || p->w_bstride <= 0) return PF_ERR_ARG;
-  if ((p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) return PF_ERR_ARG;
-  if (p->out_f32 && (p->korder & 48)) return PF_ERR_ARG;
-  if (!p->out_f32 && p->y_bstride <= 0) return PF_ERR_ARG;
-  if ((p->korder & 16) && (!p->out_exp || p->y_ld != p->Cout || p->Cout % 32)) return PF_ERR_ARG;
-  if ((p->korder & 32) && (!p->out_exp || p->y_ld < p->Cout || p->y_bstride % 4 || (reinterpret_cast<size_t>(p->y) & 7))) return PF_ERR_ARG;   // 8-byte stores
+    return pf_refuse("pf_gemm_f16x2", "argument outside the envelope (include/pf_hip.h)");
+  if (M <= 0 || M * 64 >= (1L << 31) || (long)p->w_rows * 64 >= (1L << 31) || p->x_bstride <= 0 || p->w_bstride <= 0) return pf_refuse("pf_gemm_f16x2", "argument outside the envelope (include/pf_hip.h)");
+  if ((p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) return pf_refuse("pf_gemm_f16x2", "argument outside the envelope (include/pf_hip.h)");
+  if (p->out_f32 && (p->korder & 48)) return pf_refuse("pf_gemm_f16x2", "argument outside the envelope (include/pf_hip.h)");
+  if (!p->out_f32 && p->y_bstride <= 0) return pf_refuse("pf_gemm_f16x2", "argument outside the envelope (include/pf_hip.h)");
+  if ((p->korder & 16) && (!p->out_exp || p->y_ld != p->Cout || p->Cout % 32)) return pf_refuse("pf_gemm_f16x2", "argument outside the envelope (include/pf_hip.h)");
+  if ((p->korder & 32) && (!p->out_exp || p->y_ld < p->Cout || p->y_bstride % 4 || (reinterpret_cast<size_t>(p->y) & 7))) return pf_refuse("pf_gemm_f16x2", "argument outside the envelope (include/pf_hip.h)");   // 8-byte stores
   if (f16x2_route(*p, cu_count()) == PF_S3_ROUTE_TILE160) return pf_launch_f16x2_tile160(*p, cu_count(), reinterpret_cast<hipStream_t>(stream));
   return launch_persist192_f16_linear(*p, reinterpret_cast<hipStream_t>(stream));
 }
@@ -1466,11 +1482,16 @@ extern "C" int pf_gemm_f16x2(const pf_conv_params* p, void* stream) {
 // plain bf16 linear layer through the ping-pong pipeline (see the PLAIN template parameter): x [M][x_ld] bf16, w [w_rows][Kpad] bf16
 // (packing.pack_conv), bias / scale float32, res / res2 / y bf16 (y float32 when out_f32); Cin % 64 == 0.  Tile 256 x 128, eight waves of 64 x 64.
 extern "C" int pf_gemm_bf16_pp(const pf_conv_params* p, void* stream) {
-  if (!p || !p->x || !p->w || !p->y) return PF_ERR_ARG;
-  if (p->KH != 1 || p->KW != 1 || p->stride != 1 || p->pad != 0 || p->shuffle > 1 || p->dtype != PF_DTYPE_BF16) return PF_ERR_ARG;
-  if (p->Cin <= 0 || p->Cin % 64 || p->Kpad < p->Cin || p->x_ld % 8 || p->x_ld < p->Cin || p->Kpad % 8) return PF_ERR_ARG;
-  if (p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || p->w_rows < p->Cout || (p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) return PF_ERR_ARG;
-  if ((long)p->B * p->OH * p->OW <= 0 || (long)p->B * p->OH * p->OW >= (1L << 31)) return PF_ERR_ARG;
+  if (!p || !p->x || !p->w || !p->y) return pf_refuse("pf_gemm_bf16_pp", "null tensor");
+  if (const char* e = pf_linear_envelope(*p)) return pf_refuse("pf_gemm_bf16_pp", e);
+  if (p->dtype != PF_DTYPE_BF16 || p->batch > 1) return pf_refuse("pf_gemm_bf16_pp", "bf16, one plane only");
+  if (pf_misaligned(p->x, 16) || pf_misaligned(p->w, 16) || pf_misaligned(p->y, p->out_f32 ? 16 : 8) || pf_misaligned(p->bias, 16) || pf_misaligned(p->scale, 16) ||
+      pf_misaligned(p->res, 8) || pf_misaligned(p->res2, 8))
+    return pf_refuse("pf_gemm_bf16_pp", "misaligned tensor (16 bytes; 8 for bf16 y / res / res2)");
+  if (p->y_ld < p->Cout || (p->res && p->res_ld < p->Cout) || (p->res2 && p->res2_ld < p->Cout)) return pf_refuse("pf_gemm_bf16_pp", "y_ld / residual ld below Cout");
+  if (p->Cin <= 0 || p->Cin % 64 || p->Kpad < p->Cin || p->x_ld % 8 || p->x_ld < p->Cin || p->Kpad % 8) return pf_refuse("pf_gemm_bf16_pp", "argument outside the envelope (include/pf_hip.h)");
+  if (p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || p->w_rows < p->Cout || (p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) return pf_refuse("pf_gemm_bf16_pp", "argument outside the envelope (include/pf_hip.h)");
+  if ((long)p->B * p->OH * p->OW <= 0 || (long)p->B * p->OH * p->OW >= (1L << 31)) return pf_refuse("pf_gemm_bf16_pp", "argument outside the envelope (include/pf_hip.h)");
   pf_conv_params pd = *p;
   pd.korder = 0;
   pd.x_bstride = 32;                     // "planes" = consecutive 32-deep K sub-chunks of the one bf16 matrix
@@ -1479,7 +1500,7 @@ extern "C" int pf_gemm_bf16_pp(const pf_conv_params* p, void* stream) {
 }
 
 extern "C" int pf_gemm_split3_timed(const pf_conv_params* p, int iters, float* ms, void* stream) {
-  if (!ms || iters <= 0) return PF_ERR_ARG;
+  if (!ms || iters <= 0) return pf_refuse("pf_gemm_split3_timed", "null ms or iters <= 0");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   int rc = pf_gemm_split3(p, stream);
   if (rc != PF_OK) return rc;
@@ -1512,7 +1533,9 @@ __global__ void split3_kernel(const float* __restrict__ x, int x_ld, bf16_t* __r
 }
 
 extern "C" int pf_split3(const float* x, int x_ld, void* y, int y_ld, long plane, long rows, int cols, void* stream) {
-  if (!x || !y || cols % 4 || x_ld % 4 || y_ld % 4 || rows <= 0 || plane <= 0) return PF_ERR_ARG;
+  if (!x || !y || pf_misaligned(x, 16) || pf_misaligned(y, 8)) return pf_refuse("pf_split3", "null or misaligned tensor");
+  if (cols <= 0 || cols % 4 || x_ld % 4 || y_ld % 4 || x_ld < cols || y_ld < cols || rows <= 0 || plane % 4 || plane < (rows - 1) * y_ld + cols)
+    return pf_refuse("pf_split3", "cols, x_ld, y_ld, plane must be multiples of 4, the strides >= cols, the plane must hold the rows");
   long n = rows * (cols / 4);
   long g = (n + 255) / 256;
   hipLaunchKernelGGL(split3_kernel, dim3((unsigned)(g > 16384 ? 16384 : g)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, x_ld,

@@ -20,6 +20,7 @@
 #include <atomic>
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
+#include "pf_args.h"
 
 namespace {
 
@@ -1472,13 +1473,28 @@ int validate(const pf_conv_params* p) {
   const int vec = p->dtype == PF_DTYPE_BF16 ? 8 : 4;
   const int bk = 8 * vec;
   const char* e = nullptr;
+  const char* geo = nullptr;
+  // a pixel of y holds Cout channels, Cout / s^2 under the pixel shuffle; y, res and res2 move in groups of four elements of their own type
+  const int ss = p->shuffle > 1 ? p->shuffle * p->shuffle : 1;
+  // (res / res2: the element size only -- the engine hands in residual views one element off a vector boundary, tests/test_float32_grade_gpu.py
+  // test_unaligned_residual_does_not_take_s3_1x1, and the hardware's unaligned vector loads compute them; bias / scale likewise)
+  const unsigned ya = (p->dtype == PF_DTYPE_F32 || p->out_f32) ? 16 : 8, ra = p->dtype == PF_DTYPE_F32 ? 4 : 2;
   if (!p->x || !p->w || !p->y) e = "null tensor";
-  else if (p->dtype != PF_DTYPE_F32 && p->dtype != PF_DTYPE_BF16) e = "bad dtype";
+  else if (pf_bad_dtype(p->dtype)) e = "bad dtype";
+  else if (pf_misaligned(p->x, 16) || pf_misaligned(p->w, 16) || pf_misaligned(p->bias, 4) || pf_misaligned(p->scale, 4) || pf_misaligned(p->y, ya) ||
+           pf_misaligned(p->res, ra) || pf_misaligned(p->res2, ra))
+    e = "misaligned tensor (x, w: 16 bytes; y: four elements; bias, scale, res, res2: one element)";
+  else if (pf_bad_act(p->act)) e = "bad act";
+  else if (p->shuffle < 1) e = "shuffle must be >= 1 (1 = none)";
+  else if (p->batch < 0) e = "batch must be >= 0";
+  else if ((geo = pf_conv_geometry(*p)) != nullptr) e = geo;
   else if (p->Cin <= 0 || p->Cin % vec) e = "Cin must be a positive multiple of the 16-byte vector";
   else if (p->x_ld % vec || p->x_ld < p->Cin) e = "x_ld must be a multiple of the vector and >= Cin";
   else if (p->Cout <= 0 || p->Cout % 4) e = "Cout must be a positive multiple of 4";
   else if (p->y_ld % 4 || (p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) e = "output/residual ld must be multiples of 4";
-  else if (p->Kpad % bk) e = "Kpad must be a multiple of the 128-byte chunk";
+  else if (p->y_ld < p->Cout / ss || (p->res && p->res_ld < p->Cout) || (p->res2 && p->res2_ld < p->Cout)) e = "output/residual ld below the channels of a pixel";
+  else if (p->batch > 1 && (p->x_bstride <= 0 || p->w_bstride <= 0 || p->y_bstride <= 0)) e = "batch > 1: plane strides missing";
+  else if (p->Kpad <= 0 || p->Kpad % bk) e = "Kpad must be a multiple of the 128-byte chunk";
   else if ((long)p->KH * p->KW * (p->Cin / vec) > (long)(p->Kpad / vec)) e = "Kpad smaller than KH*KW*Cin";
   else if (p->w_rows < p->Cout) e = "w_rows < Cout";
   else if (p->shuffle > 1 && (p->Cout % (p->shuffle * p->shuffle) || (p->Cout / (p->shuffle * p->shuffle)) % 4)) e = "shuffle: Cout/(s*s) must be a multiple of 4";
@@ -1496,11 +1512,13 @@ int validate(const pf_conv_params* p) {
 }  // namespace
 
 extern "C" const char* pf_last_error(void) { return g_err; }
+// (csrc/pf_args.h: the refusals of every other source file end here)
+void pf_set_error(const char* fn, const char* why) { snprintf(g_err, sizeof(g_err), "%s: %s", fn, why); }
 extern "C" int pf_version(void) { return 1; }
 extern "C" int pf_conv_last_variant(void) { return g_last_variant; }
 
 extern "C" int pf_conv(const pf_conv_params* p, void* stream) {
-  if (!p) return PF_ERR_ARG;
+  if (!p) return pf_refuse("pf_conv", "null p");
   int rc = validate(p);
   if (rc) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1510,7 +1528,7 @@ extern "C" int pf_conv(const pf_conv_params* p, void* stream) {
 }
 
 extern "C" int pf_conv_timed(const pf_conv_params* p, int iters, float* ms, void* stream) {
-  if (!p || !ms || iters <= 0) return PF_ERR_ARG;
+  if (!p || !ms || iters <= 0) return pf_refuse("pf_conv_timed", "null p / ms or iters <= 0");
   int rc = validate(p);
   if (rc) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -5,6 +5,7 @@
 #include <atomic>
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
+#include "pf_args.h"
 
 // the range pass of the fp16x2 Winograd layers (csrc/wino_f16x2.hip; not part of the C ABI)
 namespace pf_f16x2 {
@@ -313,6 +314,11 @@ __global__ void crop_resize_planar_kernel(const float* __restrict__ img, int C, 
 // torchvision roi_align, aligned=True, sampling_ratio=-1 (adaptive).  Coordinates follow the
 // torchvision kernel's float32 operation order, one rounding per operation.  (hipcc's __fmul_rn / __fadd_rn are a plain product and sum, which it
 // contracts into an fma: the coordinates then differ by an ulp from the float32 definition, 3e-5 of an output of a 28 x 37 map.  The pragma holds.)
+// the batch index of an RoI lives on the device: clamped to [0, Bf) (a NaN gives 0) instead of indexing outside the feature maps
+__device__ __forceinline__ int roi_batch(float b, int Bf) {
+  const int i = (int)fminf(fmaxf(b, 0.f), (float)(Bf - 1));
+  return i;
+}
 __device__ __forceinline__ float roi_edge(float r, float scale) {                  // r * scale - 0.5
 #pragma clang fp contract(off)
   return r * scale - 0.5f;
@@ -342,7 +348,7 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const void* __restrict__
   const int cv = (C + 7) >> 3;
   const int k = blockIdx.x / oh, ph = blockIdx.x - k * oh;
   const float* r = rois + k * 5;
-  const int b = (int)r[0];
+  const int b = roi_batch(r[0], Bf);
   const float start_w = roi_edge(r[1], scale), start_h = roi_edge(r[2], scale);
   const float end_w = roi_edge(r[3], scale), end_h = roi_edge(r[4], scale);
   const float roi_w = __fsub_rn(end_w, start_w), roi_h = __fsub_rn(end_h, start_h);
@@ -418,7 +424,7 @@ __global__ void roi_align_scalar_kernel(const float* __restrict__ feat, int Bf, 
     const int ph = (int)((i / ow) % oh);
     const int k = (int)(i / ((long)ow * oh));
     const float* r = rois + k * 5;
-    const int b = (int)r[0];
+    const int b = roi_batch(r[0], Bf);
     const float start_w = roi_edge(r[1], scale), start_h = roi_edge(r[2], scale);
     const float end_w = roi_edge(r[3], scale), end_h = roi_edge(r[4], scale);
     const float roi_w = __fsub_rn(end_w, start_w), roi_h = __fsub_rn(end_h, start_h);
@@ -681,7 +687,7 @@ __global__ void stitch_init_kernel(float* __restrict__ pred, float* __restrict__
     const int y = (int)((i / pw) % ph);
     const int p = (int)(i / ((long)pw * ph));
     const int Y = yx[2 * p] + y, X = yx[2 * p + 1] + x;
-    if (Y < MH && X < MW) {
+    if (Y >= 0 && X >= 0 && Y < MH && X < MW) {      // (yx lives on the device: a tile that starts in front of the map is clipped like one that ends behind it)
       const float m = mask[(long)y * pw + x];
       pred[(long)Y * MW + X] = depth[i] * m;
       count[(long)Y * MW + X] = m;
@@ -952,11 +958,27 @@ static int cmax_by_range_pass(const void* y, int y_ld, long P, int C, unsigned* 
   return pf_f16x2::launch_absmax(static_cast<const float*>(y), y_ld, P, C, 0, cmax, st);
 }
 
+// Refusals shared by the NHWC image kernels (PF_ERR_ARG, before any launch): sizes that are not positive, C not a multiple of 8, a pixel stride that
+// is not a multiple of 8 or is below C, more than 2^31 - 1 (batch, row) pairs or items of a row (both are 32-bit in the kernels).
+static const char* nhwc_pair(int B, int H, int W, int C, int x_ld, int OH, int OW, int y_ld) {
+  if (B <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return "B, H, W, OH, OW must be positive";
+  if (C <= 0 || C % 8) return "C must be a positive multiple of 8";
+  if (x_ld % 8 || x_ld < C) return "the input pixel stride must be a multiple of 8 and >= C";
+  if (y_ld % 8 || y_ld < C) return "y_ld must be a multiple of 8 and >= C";
+  if ((long)B * OH >= (1L << 31) || (long)B * H >= (1L << 31) || (long)OW * (C / 8) >= (1L << 31) || (long)W * (C / 4) >= (1L << 31))
+    return "too many rows or row items for 32-bit indices";
+  return nullptr;
+}
+
 // cmax != nullptr (float32 calls only): the channel maxima of the stored values are merged into cmax [C]
 static int resize_bilinear_impl(const void* x, int x_ld, int B, int H, int W, int C, void* y, int y_ld, int OH, int OW, const void* add, int add_ld,
                                 int in_f32, int out_f32, int dtype, unsigned* cmax, void* stream) {
-  if (!x || !y || C % 8 || x_ld % 8 || y_ld % 8 || (add && add_ld % 8)) return PF_ERR_ARG;
-  if (cmax && dtype != PF_DTYPE_F32) return PF_ERR_ARG;
+  if (!x || !y) return pf_refuse("pf_resize_bilinear", "null tensor");
+  if (pf_bad_dtype(dtype)) return pf_refuse("pf_resize_bilinear", "bad dtype");
+  if (pf_misaligned(x, 16) || pf_misaligned(y, 16) || pf_misaligned(add, 16) || pf_misaligned(cmax, 4)) return pf_refuse("pf_resize_bilinear", "misaligned tensor");
+  if (const char* e = nhwc_pair(B, H, W, C, x_ld, OH, OW, y_ld)) return pf_refuse("pf_resize_bilinear", e);
+  if (add && (add_ld % 8 || add_ld < C)) return pf_refuse("pf_resize_bilinear", "add_ld must be a multiple of 8 and >= C");
+  if (cmax && dtype != PF_DTYPE_F32) return pf_refuse("pf_resize_bilinear", "channel maxima: float32 calls only");
   const bool homogeneous = dtype == PF_DTYPE_BF16 ? (!in_f32 && !out_f32) : true;      // (dtype f32: everything is float32)
   if (homogeneous && resize_v2()) {
     const ResizeSrc s0{x, x_ld, H, W, C, ac_scale(H, OH), ac_scale(W, OW)};
@@ -981,12 +1003,19 @@ extern "C" int pf_resize_bilinear_ex(const void* x, int x_ld, int B, int H, int 
 
 static int resize_concat_impl(const void* const* xs, const int* lds, const int* Hs, const int* Ws, const int* Cs, int nsrc, int B,
                               void* y, int y_ld, int OH, int OW, int dtype, unsigned* cmax, void* stream) {
-  if (!xs || !lds || !Hs || !Ws || !Cs || !y || nsrc < 2 || nsrc > 3 || y_ld % 8) return PF_ERR_ARG;
-  if (cmax && dtype != PF_DTYPE_F32) return PF_ERR_ARG;
+  if (!xs || !lds || !Hs || !Ws || !Cs || !y) return pf_refuse("pf_resize_concat", "null pointer");
+  if (nsrc < 2 || nsrc > 3) return pf_refuse("pf_resize_concat", "nsrc must be 2 or 3");
+  if (pf_bad_dtype(dtype)) return pf_refuse("pf_resize_concat", "bad dtype");
+  if (pf_misaligned(y, 16) || pf_misaligned(cmax, 4)) return pf_refuse("pf_resize_concat", "misaligned tensor");
+  if (cmax && dtype != PF_DTYPE_F32) return pf_refuse("pf_resize_concat", "channel maxima: float32 calls only");
   ResizeSrc s[3] = {};
   long cv = 0;
+  for (int i = 0; i < nsrc; ++i) cv += Cs[i] > 0 ? Cs[i] / 8 : 0;
+  if (cv * 8 > y_ld) return pf_refuse("pf_resize_concat", "y_ld below the sum of the channels");
+  cv = 0;
   for (int i = 0; i < nsrc; ++i) {
-    if (!xs[i] || Cs[i] % 8 || lds[i] % 8) return PF_ERR_ARG;
+    if (!xs[i] || pf_misaligned(xs[i], 16)) return pf_refuse("pf_resize_concat", "null or misaligned source");
+    if (const char* e = nhwc_pair(B, Hs[i], Ws[i], Cs[i], lds[i], OH, OW, y_ld)) return pf_refuse("pf_resize_concat", e);
     s[i] = ResizeSrc{xs[i], lds[i], Hs[i], Ws[i], Cs[i], ac_scale(Hs[i], OH), ac_scale(Ws[i], OW)};
     cv += Cs[i] / 8;
   }
@@ -1012,7 +1041,10 @@ extern "C" int pf_resize_concat_ex(const void* const* xs, const int* lds, const 
 }
 
 extern "C" int pf_crop_resize_planar(const float* img, int C, int H, int W, const int* boxes, int P, float* out, int oh, int ow, void* stream) {
-  if (!img || !boxes || !out) return PF_ERR_ARG;
+  if (!img || !boxes || !out) return pf_refuse("pf_crop_resize_planar", "null pointer");
+  if (pf_misaligned(img, 4) || pf_misaligned(boxes, 4) || pf_misaligned(out, 4)) return pf_refuse("pf_crop_resize_planar", "misaligned pointer");
+  if (C <= 0 || H <= 0 || W <= 0 || P <= 0 || oh <= 0 || ow <= 0) return pf_refuse("pf_crop_resize_planar", "C, H, W, P, oh, ow must be positive");
+  if ((long)P * 4 >= (1L << 31)) return pf_refuse("pf_crop_resize_planar", "too many boxes");
   const long total = (long)P * C * oh * ow;
   hipLaunchKernelGGL(crop_resize_planar_kernel, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), img, C, H, W, boxes, P, out, oh, ow);
   return ok();
@@ -1020,15 +1052,22 @@ extern "C" int pf_crop_resize_planar(const float* img, int C, int H, int W, cons
 
 static int roi_align_impl(const void* feat, int f_ld, int Bf, int H, int W, int C, const float* rois, int K, void* y, int y_ld,
                           int oh, int ow, float spatial_scale, int in_f32, int out_f32, int dtype, unsigned* cmax, void* stream) {
-  if (!feat || !rois || !y) return PF_ERR_ARG;
-  if (cmax && (dtype != PF_DTYPE_F32 || C == 1 || C > 8192)) return PF_ERR_ARG;      // (maxima: float32 NHWC maps; one LDS word per channel)
+  if (!feat || !rois || !y) return pf_refuse("pf_roi_align", "null pointer");
+  if (pf_bad_dtype(dtype)) return pf_refuse("pf_roi_align", "bad dtype");
+  if (Bf <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || oh <= 0 || ow <= 0) return pf_refuse("pf_roi_align", "Bf, H, W, C, K, oh, ow must be positive");
+  if (!(spatial_scale > 0.f)) return pf_refuse("pf_roi_align", "spatial_scale must be positive");
+  if (pf_misaligned(rois, 4) || pf_misaligned(cmax, 4) || (long)K * 5 >= (1L << 31)) return pf_refuse("pf_roi_align", "misaligned or too many rois");
+  if (cmax && (dtype != PF_DTYPE_F32 || C == 1 || C > 8192))      // (maxima: float32 NHWC maps; one LDS word per channel)
+    return pf_refuse("pf_roi_align", "channel maxima: float32 NHWC maps with C <= 8192 only");
   if (C == 1) {  // planar float depth map
-    if (!in_f32 || !out_f32) return PF_ERR_ARG;
+    if (!in_f32 || !out_f32) return pf_refuse("pf_roi_align", "the planar C = 1 form is float32 in and out");
+    if (pf_misaligned(feat, 4) || pf_misaligned(y, 4)) return pf_refuse("pf_roi_align", "misaligned tensor");
     hipLaunchKernelGGL(roi_align_scalar_kernel, dim3(grid_for((long)K * oh * ow, 256)), dim3(256), 0, ST(stream), (const float*)feat, Bf, H, W, rois, K, (float*)y, oh, ow, spatial_scale);
     return ok();
   }
-  if (C % 8 || f_ld % 8 || y_ld % 8) return PF_ERR_ARG;
-  if ((long)K * oh >= (1L << 31) || (long)(ow / 4 + 1) * (C / 8) >= (1L << 31)) return PF_ERR_ARG;
+  if (C % 8 || f_ld % 8 || y_ld % 8 || f_ld < C || y_ld < C) return pf_refuse("pf_roi_align", "C, f_ld, y_ld must be multiples of 8, the strides >= C");
+  if (pf_misaligned(feat, 16) || pf_misaligned(y, 16)) return pf_refuse("pf_roi_align", "misaligned tensor");
+  if ((long)K * oh >= (1L << 31) || (long)(ow / 4 + 1) * (C / 8) >= (1L << 31)) return pf_refuse("pf_roi_align", "too many output rows or row items");
   const unsigned rows = (unsigned)((long)K * oh);
   if (dtype == PF_DTYPE_BF16)
     hipLaunchKernelGGL(roi_align_kernel<bf16_t>, dim3(rows), dim3(256), 0, ST(stream), feat, f_ld, Bf, H, W, C, rois, K, y, y_ld, oh, ow, spatial_scale, in_f32, out_f32, NOCMAX);
@@ -1051,29 +1090,44 @@ extern "C" int pf_roi_align_ex(const void* feat, int f_ld, int Bf, int H, int W,
 }
 
 extern "C" int pf_maxpool2(const void* x, int x_ld, int B, int H, int W, int C, void* y, int y_ld, int dtype, void* stream) {
-  if (!x || !y || C % 8 || x_ld % 8 || y_ld % 8) return PF_ERR_ARG;
+  if (!x || !y) return pf_refuse("pf_maxpool2", "null tensor");
+  if (pf_bad_dtype(dtype)) return pf_refuse("pf_maxpool2", "bad dtype");
+  if (pf_misaligned(x, 16) || pf_misaligned(y, 16)) return pf_refuse("pf_maxpool2", "misaligned tensor");
+  if (B <= 0 || H < 2 || W < 2) return pf_refuse("pf_maxpool2", "B must be positive, H and W >= 2");
+  if (C <= 0 || C % 8 || x_ld % 8 || y_ld % 8 || x_ld < C || y_ld < C) return pf_refuse("pf_maxpool2", "C must be a positive multiple of 8, x_ld and y_ld multiples of 8 >= C");
   const long total = (long)B * (H / 2) * (W / 2) * (C / 8);
   if (dtype == PF_DTYPE_BF16) hipLaunchKernelGGL(maxpool2_kernel<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), (const bf16_t*)x, x_ld, B, H, W, C, (bf16_t*)y, y_ld);
   else hipLaunchKernelGGL(maxpool2_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), (const float*)x, x_ld, B, H, W, C, (float*)y, y_ld);
   return ok();
 }
 
+// the channel-slice copy: refused are null pointers, tensors off a 16-byte boundary, npix <= 0, C not a positive multiple of 8, a pixel stride that is
+// not a multiple of 8 or is below C, an unknown dtype
+static const char* copy_envelope(const void* x, int x_ld, const void* y, int y_ld, long npix, int C, int dtype) {
+  if (!x || !y) return "null tensor";
+  if (pf_bad_dtype(dtype)) return "bad dtype";
+  if (pf_misaligned(x, 16) || pf_misaligned(y, 16)) return "misaligned tensor";
+  if (npix <= 0 || C <= 0 || C % 8 || x_ld % 8 || y_ld % 8 || x_ld < C || y_ld < C) return "npix must be positive, C a positive multiple of 8, x_ld and y_ld multiples of 8 >= C";
+  return nullptr;
+}
+
 extern "C" int pf_copy_channels(const void* x, int x_ld, void* y, int y_ld, long npix, int C, int in_f32, int out_f32, int dtype, void* stream) {
-  if (!x || !y || C % 8 || x_ld % 8 || y_ld % 8) return PF_ERR_ARG;
+  if (const char* e = copy_envelope(x, x_ld, y, y_ld, npix, C, dtype)) return pf_refuse("pf_copy_channels", e);
   const long total = npix * (C / 8);
   LAUNCH_T(copy_channels_kernel, total, x, x_ld, y, y_ld, npix, C, in_f32, out_f32, NOCMAX);
   return ok();
 }
 
 extern "C" int pf_zero_u32(void* p, long n, void* stream) {
-  if (!p || n <= 0) return PF_ERR_ARG;
+  if (!p || n <= 0 || pf_misaligned(p, 4)) return pf_refuse("pf_zero_u32", "null or misaligned pointer, or n <= 0");
   return hipMemsetAsync(p, 0, (size_t)n * 4, ST(stream)) == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
 }
 
 extern "C" int pf_copy_channels_ex(const void* x, int x_ld, void* y, int y_ld, long npix, int C, int in_f32, int out_f32, int dtype, void* cmax,
                                    void* stream) {
   if (!cmax) return pf_copy_channels(x, x_ld, y, y_ld, npix, C, in_f32, out_f32, dtype, stream);
-  if (!x || !y || C % 8 || x_ld % 8 || y_ld % 8 || dtype != PF_DTYPE_F32 || C > 8192) return PF_ERR_ARG;
+  if (const char* e = copy_envelope(x, x_ld, y, y_ld, npix, C, dtype)) return pf_refuse("pf_copy_channels_ex", e);
+  if (dtype != PF_DTYPE_F32 || C > 8192 || pf_misaligned(cmax, 4)) return pf_refuse("pf_copy_channels_ex", "channel maxima: float32 calls with C <= 8192, a 4-byte aligned vector");
   const long total = npix * (C / 8);
   hipLaunchKernelGGL((copy_channels_kernel<float, true>), dim3(grid_for(total, 256)), dim3(256), (size_t)C * 4, ST(stream), x, x_ld, y, y_ld, npix, C, in_f32,
                      out_f32, static_cast<unsigned*>(cmax));
@@ -1081,7 +1135,10 @@ extern "C" int pf_copy_channels_ex(const void* x, int x_ld, void* y, int y_ld, l
 }
 
 extern "C" int pf_pack_fusion_input(const float* cdepth, const float* fdepth, const float* crops, void* y, int B, int h, int w, int dtype, void* stream) {
-  if (!cdepth || !fdepth || !crops || !y) return PF_ERR_ARG;
+  if (!cdepth || !fdepth || !crops || !y) return pf_refuse("pf_pack_fusion_input", "null tensor");
+  if (pf_bad_dtype(dtype)) return pf_refuse("pf_pack_fusion_input", "bad dtype");
+  if (pf_misaligned(cdepth, 4) || pf_misaligned(fdepth, 4) || pf_misaligned(crops, 4) || pf_misaligned(y, 16)) return pf_refuse("pf_pack_fusion_input", "misaligned tensor");
+  if (B <= 0 || h <= 0 || w <= 0) return pf_refuse("pf_pack_fusion_input", "B, h, w must be positive");
   const long total = (long)B * h * w;
   if (dtype == PF_DTYPE_BF16) hipLaunchKernelGGL(pack_fusion_input_kernel<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), cdepth, fdepth, crops, (bf16_t*)y, B, h, w);
   else hipLaunchKernelGGL(pack_fusion_input_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), cdepth, fdepth, crops, (float*)y, B, h, w);
@@ -1089,7 +1146,10 @@ extern "C" int pf_pack_fusion_input(const float* cdepth, const float* fdepth, co
 }
 
 extern "C" int pf_nhwc_to_nchw_f32(const void* x, int x_ld, float* y, int B, int H, int W, int C, int in_f32, int dtype, void* stream) {
-  if (!x || !y) return PF_ERR_ARG;
+  if (!x || !y) return pf_refuse("pf_nhwc_to_nchw_f32", "null tensor");
+  if (pf_bad_dtype(dtype)) return pf_refuse("pf_nhwc_to_nchw_f32", "bad dtype");
+  if (pf_misaligned(x, (in_f32 || dtype == PF_DTYPE_F32) ? 4 : 2) || pf_misaligned(y, 4)) return pf_refuse("pf_nhwc_to_nchw_f32", "misaligned tensor");
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || x_ld < C) return pf_refuse("pf_nhwc_to_nchw_f32", "B, H, W, C must be positive, x_ld >= C");
   const long total = (long)B * C * H * W;
   LAUNCH_T(nhwc_to_nchw_kernel, total, x, x_ld, y, B, H, W, C, in_f32);
   return ok();
@@ -1097,7 +1157,11 @@ extern "C" int pf_nhwc_to_nchw_f32(const void* x, int x_ld, float* y, int B, int
 
 extern "C" int pf_attractor(const float* A, int a_ld, int n_attr, int a_stride, float a_eps, int attractor_exp, int kind_sum,
                             const float* b_prev, int hp, int wp, float* out, int B, int h, int w, int n_bins, void* stream) {
-  if (!A || !b_prev || !out || n_bins % 4 || n_attr < 1 || a_stride < 1) return PF_ERR_ARG;
+  if (!A || !b_prev || !out) return pf_refuse("pf_attractor", "null tensor");
+  if (pf_misaligned(A, 4) || pf_misaligned(b_prev, 16) || pf_misaligned(out, 16)) return pf_refuse("pf_attractor", "misaligned tensor");
+  if (n_bins <= 0 || n_bins % 4 || n_attr < 1 || a_stride < 1 || (long)(n_attr - 1) * a_stride + 1 > a_ld)
+    return pf_refuse("pf_attractor", "n_bins must be a positive multiple of 4, n_attr, a_stride >= 1, a_ld must hold the attractors");
+  if (B <= 0 || h <= 0 || w <= 0 || hp <= 0 || wp <= 0) return pf_refuse("pf_attractor", "B, h, w, hp, wp must be positive");
   const long total = (long)B * h * w * (n_bins / 4);
   const float scale = kind_sum ? 1.0f : 1.0f / (float)n_attr;
   if (attractor_exp)
@@ -1111,14 +1175,16 @@ extern "C" int pf_attractor(const float* A, int a_ld, int n_attr, int a_stride, 
 
 extern "C" int pf_seed_bin_centers(const float* x, int x_ld, float* out, long npix, int n_bins, float min_depth, float max_depth,
                                    int bounded, int normalize, void* stream) {
-  if (!x || !out || npix <= 0 || n_bins < 1 || x_ld < n_bins) return PF_ERR_ARG;
+  if (!x || !out || pf_misaligned(x, 4) || pf_misaligned(out, 4)) return pf_refuse("pf_seed_bin_centers", "null or misaligned tensor");
+  if (npix <= 0 || n_bins < 1 || x_ld < n_bins) return pf_refuse("pf_seed_bin_centers", "npix, n_bins must be positive, x_ld >= n_bins");
   hipLaunchKernelGGL(seed_bin_centers_kernel, dim3(grid_for(npix, 64)), dim3(64), 0, ST(stream), x, x_ld, out, npix, n_bins, min_depth,
                      max_depth, bounded, normalize);
   return ok();
 }
 
 extern "C" int pf_bounded_bin_centers(const float* b, float* out, long npix, int n_bins, float min_depth, float max_depth, void* stream) {
-  if (!b || !out || npix <= 0 || n_bins < 1 || n_bins > 64) return PF_ERR_ARG;
+  if (!b || !out || pf_misaligned(b, 4) || pf_misaligned(out, 4)) return pf_refuse("pf_bounded_bin_centers", "null or misaligned tensor");
+  if (npix <= 0 || n_bins < 1 || n_bins > 64) return pf_refuse("pf_bounded_bin_centers", "npix must be positive, n_bins in [1, 64]");
   hipLaunchKernelGGL(bounded_centers_kernel, dim3(grid_for(npix * 64, 256)), dim3(256), 0, ST(stream), b, out, npix, n_bins, min_depth,
                      max_depth);
   return ok();
@@ -1126,7 +1192,10 @@ extern "C" int pf_bounded_bin_centers(const float* b, float* out, long npix, int
 
 extern "C" int pf_logbinom_depth(const float* pt, int pt_ld, const float* centers, int hc, int wc, float* depth, int B, int h, int w,
                                  int n_bins, float min_temp, float max_temp, void* stream) {
-  if (!pt || !centers || !depth || n_bins % 4 || n_bins > 256) return PF_ERR_ARG;
+  if (!pt || !centers || !depth) return pf_refuse("pf_logbinom_depth", "null tensor");
+  if (pf_misaligned(pt, 4) || pf_misaligned(centers, 16) || pf_misaligned(depth, 4)) return pf_refuse("pf_logbinom_depth", "misaligned tensor");
+  if (n_bins <= 0 || n_bins % 4 || n_bins > 256 || pt_ld < 4) return pf_refuse("pf_logbinom_depth", "n_bins must be a multiple of 4 in [4, 256], pt_ld >= 4");
+  if (B <= 0 || h <= 0 || w <= 0 || hc <= 0 || wc <= 0) return pf_refuse("pf_logbinom_depth", "B, h, w, hc, wc must be positive");
   const long total = (long)B * h * w;
   hipLaunchKernelGGL(logbinom_depth_kernel, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), pt, pt_ld, centers, hc, wc, depth, B, h, w, n_bins, min_temp, max_temp, ac_scale(hc, h), ac_scale(wc, w));
   return ok();
@@ -1134,31 +1203,40 @@ extern "C" int pf_logbinom_depth(const float* pt, int pt_ld, const float* center
 
 extern "C" int pf_stitch_init(float* pred, float* count, int MH, int MW, const float* depth, const float* mask, const int* yx, int P,
                               int ph, int pw, void* stream) {
-  if (!pred || !count || !depth || !mask || !yx) return PF_ERR_ARG;
+  if (!pred || !count || !depth || !mask || !yx) return pf_refuse("pf_stitch_init", "null pointer");
+  if (pf_misaligned(pred, 4) || pf_misaligned(count, 4) || pf_misaligned(depth, 4) || pf_misaligned(mask, 4) || pf_misaligned(yx, 4)) return pf_refuse("pf_stitch_init", "misaligned pointer");
+  if (MH <= 0 || MW <= 0 || P <= 0 || ph <= 0 || pw <= 0 || (long)P * 2 >= (1L << 31)) return pf_refuse("pf_stitch_init", "MH, MW, P, ph, pw must be positive");
   const long total = (long)P * ph * pw;
   hipLaunchKernelGGL(stitch_init_kernel, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), pred, count, MH, MW, depth, mask, yx, P, ph, pw);
   return ok();
 }
 extern "C" int pf_stitch_finish_init(float* avg, const float* pred, const float* count, long n, void* stream) {
-  if (!avg || !pred || !count) return PF_ERR_ARG;
+  if (!avg || !pred || !count || n <= 0) return pf_refuse("pf_stitch_finish_init", "null tensor or n <= 0");
+  if (pf_misaligned(avg, 4) || pf_misaligned(pred, 4) || pf_misaligned(count, 4)) return pf_refuse("pf_stitch_finish_init", "misaligned tensor");
   hipLaunchKernelGGL(div_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ST(stream), avg, pred, count, n);
   return ok();
 }
 extern "C" int pf_stitch_update(float* avg, float* count, int MH, int MW, const float* depth, int dh, int dw, const float* mask, int y0,
                                 int x0, int ph, int pw, void* stream) {
-  if (!avg || !count || !depth || !mask) return PF_ERR_ARG;
+  if (!avg || !count || !depth || !mask) return pf_refuse("pf_stitch_update", "null tensor");
+  if (pf_misaligned(avg, 4) || pf_misaligned(count, 4) || pf_misaligned(depth, 4) || pf_misaligned(mask, 4)) return pf_refuse("pf_stitch_update", "misaligned tensor");
+  if (MH <= 0 || MW <= 0 || dh <= 0 || dw <= 0 || ph <= 0 || pw <= 0) return pf_refuse("pf_stitch_update", "MH, MW, dh, dw, ph, pw must be positive");
+  // (the kernel clips the paste window at the far edges of the map; a window that starts in front of it would write before the first element)
+  if (y0 < 0 || x0 < 0 || y0 >= MH || x0 >= MW) return pf_refuse("pf_stitch_update", "the paste window must start inside the map");
   const long total = (long)ph * pw;
   hipLaunchKernelGGL(stitch_update_kernel, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), avg, count, MH, MW, depth, dh, dw, mask, y0, x0, ph, pw, (float)dh / (float)ph, (float)dw / (float)pw);
   return ok();
 }
 extern "C" int pf_resize_nearest_f32(const float* x, int H, int W, float* y, int OH, int OW, void* stream) {
-  if (!x || !y) return PF_ERR_ARG;
+  if (!x || !y || pf_misaligned(x, 4) || pf_misaligned(y, 4)) return pf_refuse("pf_resize_nearest_f32", "null or misaligned tensor");
+  if (H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return pf_refuse("pf_resize_nearest_f32", "H, W, OH, OW must be positive");
   const long total = (long)OH * OW;
   hipLaunchKernelGGL(resize_nearest_kernel, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), x, H, W, y, OH, OW, (float)H / (float)OH, (float)W / (float)OW);
   return ok();
 }
 extern "C" int pf_resize_bilinear_f32(const float* x, int H, int W, float* y, int OH, int OW, void* stream) {
-  if (!x || !y) return PF_ERR_ARG;
+  if (!x || !y || pf_misaligned(x, 4) || pf_misaligned(y, 4)) return pf_refuse("pf_resize_bilinear_f32", "null or misaligned tensor");
+  if (H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return pf_refuse("pf_resize_bilinear_f32", "H, W, OH, OW must be positive");
   const long total = (long)OH * OW;
   hipLaunchKernelGGL(resize_bilinear_f32_kernel, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), x, H, W, y, OH, OW, ac_scale(H, OH), ac_scale(W, OW));
   return ok();
@@ -1169,7 +1247,11 @@ extern "C" int pf_bins_tail(const float* clb, int clb_ld, int rel_off, const flo
                             float min_temp, float max_temp, void* stream) {
   if (!clb || !emb || !w0f || !b0 || !w2 || !b2 || !centers || !depth || clb_ld % 4 || (nq != 10 && nq != 11) || (nq == 11 && (rel_off % 4 || rel_off + 8 > clb_ld)) ||
       clb_ld < 32 || B <= 0 || H <= 0 || W <= 0)
-    return PF_ERR_ARG;
+    return pf_refuse("pf_bins_tail", "null tensor, clb_ld not a multiple of 4 >= 32, nq not 10 / 11, rel slice outside the row, or an empty map");
+  if (he <= 0 || we <= 0 || hc <= 0 || wc <= 0 || (nq == 11 && rel_off < 0)) return pf_refuse("pf_bins_tail", "he, we, hc, wc must be positive, rel_off >= 0");
+  if (pf_misaligned(clb, 16) || pf_misaligned(emb, 16) || pf_misaligned(w0f, 16) || pf_misaligned(centers, 16) || pf_misaligned(b0, 4) || pf_misaligned(w2, 4) ||
+      pf_misaligned(b2, 4) || pf_misaligned(depth, 4))
+    return pf_refuse("pf_bins_tail", "misaligned tensor");
   const size_t lds = (size_t)nq * BT_HID_FRAGS * 64 * 16 + 320 * 4 + 64 * 4;
   static std::atomic<unsigned long long> done{0};
   int dev = 0;

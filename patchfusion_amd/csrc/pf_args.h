@@ -1,0 +1,38 @@
+// Host side of the C ABI: the argument checks that the launchers share.  Every launcher refuses (PF_ERR_ARG) what its kernels cannot address BEFORE
+// anything is launched; include/pf_hip.h states the refusals per entry point and tests/envelope.py lists them row by row.
+#pragma once
+#include <stdint.h>
+#include "pf_common.h"
+#include "../../include/pf_hip.h"
+
+// the text behind pf_last_error(): "<entry point>: <reason>" (csrc/igemm.hip owns the thread-local buffer)
+void pf_set_error(const char* fn, const char* why);
+inline int pf_refuse(const char* fn, const char* why) {
+  pf_set_error(fn, why);
+  return PF_ERR_ARG;
+}
+
+inline bool pf_bad_dtype(int dtype) { return dtype != PF_DTYPE_F32 && dtype != PF_DTYPE_BF16; }
+inline bool pf_bad_act(int act) { return act < PF_ACT_NONE || act > PF_ACT_SOFTPLUS; }
+
+// sizes of a convolution described by pf_conv_params: everything positive and the output grid the one the input, the filter, the stride and the
+// padding give (the kernels bound-check taps against H x W but index y by OH x OW)
+inline const char* pf_conv_geometry(const pf_conv_params& p) {
+  if (p.B <= 0 || p.H <= 0 || p.W <= 0 || p.OH <= 0 || p.OW <= 0) return "B, H, W, OH, OW must be positive";
+  if (p.KH <= 0 || p.KW <= 0 || p.stride <= 0 || p.pad < 0) return "KH, KW, stride must be positive, pad >= 0";
+  if (p.H + 2L * p.pad < p.KH || p.W + 2L * p.pad < p.KW) return "filter larger than the padded input";
+  if ((p.H + 2L * p.pad - p.KH) / p.stride + 1 != p.OH || (p.W + 2L * p.pad - p.KW) / p.stride + 1 != p.OW)
+    return "OH, OW must be (H + 2 pad - KH) / stride + 1, (W + 2 pad - KW) / stride + 1";
+  return nullptr;
+}
+
+// a pf_conv_params used as a LINEAR layer (the split-precision, fp16x2 and bf16 ping-pong GEMMs): M = B * OH * OW rows, 1 x 1 / stride 1 / no
+// padding / no pixel shuffle, a known activation, at most 65535 planes
+inline const char* pf_linear_envelope(const pf_conv_params& p) {
+  if (p.KH != 1 || p.KW != 1 || p.stride != 1 || p.pad != 0 || p.shuffle != 1) return "1x1 / stride 1 / pad 0 / shuffle 1 (linear layers) only";
+  if (const char* e = pf_conv_geometry(p)) return e;
+  if (pf_bad_act(p.act)) return "bad act";
+  if (p.batch < 0 || p.batch > PF_GRID_YZ_MAX) return "batch must be in [0, 65535]";
+  if (p.Cin <= 0 || p.Cout <= 0) return "Cin, Cout must be positive";
+  return nullptr;
+}

@@ -162,3 +162,9 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
 #define PF_OK 0
 #define PF_ERR_ARG 1
 #define PF_ERR_LAUNCH 2
+
+// host side of the C ABI: is `p` off an n-byte boundary (n a power of two: the width of the widest load or store the kernel issues through it)?
+// A null pointer counts as aligned: the launchers test optional operands with it.
+inline bool pf_misaligned(const void* p, unsigned n) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(n - 1)) != 0; }
+// a grid dimension y / z may not exceed 65535
+#define PF_GRID_YZ_MAX 65535L

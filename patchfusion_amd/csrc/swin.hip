@@ -6,6 +6,7 @@
 #include <atomic>
 #include <cstdlib>
 #include "../../include/pf_hip.h"
+#include "pf_args.h"
 
 namespace {
 
@@ -359,10 +360,27 @@ inline bool swin_mfma_enabled() {          // (read per call: 24 launches per im
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
 
+// Refusals of the four entry points (PF_ERR_ARG, before any launch): null pointers; tensors off a 16-byte boundary (the parameter vectors and tables:
+// 4 bytes); B, H, W (Hp, Wp) not positive; C not a positive multiple of 8; a leading dimension that is not a multiple of 8 or is below C; shift
+// outside [0, 12); an unknown dtype; more than 2^31 - 1 tokens; and per entry what is said at it.
+static const char* swin_map(int B, int H, int W, int C, int shift, int dtype) {
+  if (pf_bad_dtype(dtype)) return "bad dtype";
+  if (B <= 0 || H <= 0 || W <= 0) return "B, H, W must be positive";
+  if (C <= 0 || C % 8) return "C must be a positive multiple of 8";
+  if (shift < 0 || shift >= WIN) return "shift must be in [0, 12)";
+  const long Hp = (H + WIN - 1) / WIN * WIN, Wp = (W + WIN - 1) / WIN * WIN;
+  if ((long)B * Hp * Wp >= (1L << 31)) return "too many tokens";
+  return nullptr;
+}
+
 extern "C" int pf_swin_ln_partition(const void* x, int x_ld, void* xw, const float* g, const float* b, float eps, int B,
                                     int H, int W, int C, int shift, int dtype, void* stream) {
   const int G = C / 8;
-  if (!x || !xw || !g || !b || C % 8 || (G & (G - 1)) || G > 64 || G < 1 || x_ld % 8) return PF_ERR_ARG;
+  if (!x || !xw || !g || !b) return pf_refuse("pf_swin_ln_partition", "null tensor");
+  if (pf_misaligned(x, 16) || pf_misaligned(xw, 16) || pf_misaligned(g, 4) || pf_misaligned(b, 4)) return pf_refuse("pf_swin_ln_partition", "misaligned tensor");
+  if (const char* e = swin_map(B, H, W, C, shift, dtype)) return pf_refuse("pf_swin_ln_partition", e);
+  if ((G & (G - 1)) || G > 64 || G < 1) return pf_refuse("pf_swin_ln_partition", "C / 8 must be a power of two <= 64");      // (a token = G lanes of one wave)
+  if (x_ld % 8 || x_ld < C) return pf_refuse("pf_swin_ln_partition", "x_ld must be a multiple of 8 and >= C");
   const int Hp = (H + WIN - 1) / WIN * WIN, Wp = (W + WIN - 1) / WIN * WIN;
   const long ntok = (long)B * Hp * Wp;
   const int tpb = 256 / G;
@@ -372,11 +390,18 @@ extern "C" int pf_swin_ln_partition(const void* x, int x_ld, void* xw, const flo
   return ok();
 }
 
+// also refused: Hp, Wp not multiples of 12; heads <= 0 or not dividing C; a head_dim C / heads outside {2, 4, 8, 16, 32}; more than 65535 heads
+// (grid dimension y); more than 2^31 - 1 windows
 extern "C" int pf_swin_window_attention(const void* qkv, void* out, const float* bias_table, int B, int Hp, int Wp, int C,
                                         int heads, int shift, int dtype, void* stream) {
-  if (!qkv || !out || !bias_table || Hp % WIN || Wp % WIN || C % heads) return PF_ERR_ARG;
-  if (dtype == PF_DTYPE_BF16) return launch_wattn<bf16_t>((const bf16_t*)qkv, (bf16_t*)out, bias_table, B, Hp, Wp, C, heads, shift, ST(stream));
+  if (!qkv || !out || !bias_table) return pf_refuse("pf_swin_window_attention", "null tensor");
+  if (pf_misaligned(qkv, 16) || pf_misaligned(out, 16) || pf_misaligned(bias_table, 4)) return pf_refuse("pf_swin_window_attention", "misaligned tensor");
+  if (const char* e = swin_map(B, Hp, Wp, C, shift, dtype)) return pf_refuse("pf_swin_window_attention", e);
+  if (Hp % WIN || Wp % WIN) return pf_refuse("pf_swin_window_attention", "Hp, Wp must be multiples of 12");
+  if (heads <= 0 || heads > PF_GRID_YZ_MAX || C % heads) return pf_refuse("pf_swin_window_attention", "heads must be in [1, 65535] and divide C");
   const int hd = C / heads;
+  if (hd != 2 && hd != 4 && hd != 8 && hd != 16 && hd != 32) return pf_refuse("pf_swin_window_attention", "head_dim must be 2, 4, 8, 16 or 32");
+  if (dtype == PF_DTYPE_BF16) return launch_wattn<bf16_t>((const bf16_t*)qkv, (bf16_t*)out, bias_table, B, Hp, Wp, C, heads, shift, ST(stream));
   if (C % 32 == 0 && swin_mfma_enabled()) {
     const float* q = (const float*)qkv;
     float* o = (float*)out;
@@ -394,15 +419,23 @@ extern "C" int pf_swin_window_attention(const void* qkv, void* out, const float*
 
 extern "C" int pf_swin_unpartition_add(const void* proj, const void* shortcut, int s_ld, void* y, int y_ld, int B, int H,
                                        int W, int C, int shift, int dtype, void* stream) {
-  if (!proj || !shortcut || !y || C % 8 || s_ld % 8 || y_ld % 8) return PF_ERR_ARG;
+  if (!proj || !shortcut || !y) return pf_refuse("pf_swin_unpartition_add", "null tensor");
+  if (pf_misaligned(proj, 16) || pf_misaligned(shortcut, 16) || pf_misaligned(y, 16)) return pf_refuse("pf_swin_unpartition_add", "misaligned tensor");
+  if (const char* e = swin_map(B, H, W, C, shift, dtype)) return pf_refuse("pf_swin_unpartition_add", e);
+  if (s_ld % 8 || y_ld % 8 || s_ld < C || y_ld < C) return pf_refuse("pf_swin_unpartition_add", "s_ld, y_ld must be multiples of 8 and >= C");
   const long total = (long)B * H * W * (C / 8);
   if (dtype == PF_DTYPE_BF16) hipLaunchKernelGGL(swin_unpartition_add_kernel<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), (const bf16_t*)proj, (const bf16_t*)shortcut, s_ld, (bf16_t*)y, y_ld, B, H, W, C, shift);
   else hipLaunchKernelGGL(swin_unpartition_add_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), (const float*)proj, (const float*)shortcut, s_ld, (float*)y, y_ld, B, H, W, C, shift);
   return ok();
 }
 
+// x [B][T][x_ld] += pos [T][C]: refused are null / misaligned pointers, B, T not positive, C not a positive multiple of 8, x_ld not a multiple of 8 or below C,
+// an unknown dtype
 extern "C" int pf_add_rowwise(void* x, int x_ld, const float* pos, int B, int T, int C, int dtype, void* stream) {
-  if (!x || !pos || C % 8 || x_ld % 8) return PF_ERR_ARG;
+  if (!x || !pos) return pf_refuse("pf_add_rowwise", "null tensor");
+  if (pf_bad_dtype(dtype)) return pf_refuse("pf_add_rowwise", "bad dtype");
+  if (pf_misaligned(x, 16) || pf_misaligned(pos, 4)) return pf_refuse("pf_add_rowwise", "misaligned tensor");
+  if (B <= 0 || T <= 0 || C <= 0 || C % 8 || x_ld % 8 || x_ld < C) return pf_refuse("pf_add_rowwise", "B, T must be positive, C a positive multiple of 8, x_ld a multiple of 8 >= C");
   const long total = (long)B * T * (C / 8);
   if (dtype == PF_DTYPE_BF16) hipLaunchKernelGGL(add_rowwise_kernel<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), (bf16_t*)x, x_ld, pos, B, T, C);
   else hipLaunchKernelGGL(add_rowwise_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), (float*)x, x_ld, pos, B, T, C);

@@ -1,9 +1,12 @@
 // ViT (DINOv2) encoder kernels other than the linear layers (those run on igemm.hip):
 // patch im2col + ImageNet normalisation, token assembly, LayerNorm, qkv head split and the fused
 // softmax attention on the matrix cores.
+#include <atomic>
+#include <mutex>
 #include <type_traits>
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
+#include "pf_args.h"
 
 namespace {
 
@@ -1098,8 +1101,15 @@ inline int ok() { return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
 
+// Every launcher below refuses (PF_ERR_ARG, message through pf_last_error) what its kernel cannot address: null or misaligned pointers (16 bytes
+// wherever the kernel moves 8-channel vectors, the element size for scalar accesses), sizes that are not positive, leading dimensions below the
+// row they hold, an unknown dtype, and a grid dimension y above 65535.  Nothing is launched before the checks pass.
+
 extern "C" int pf_patch_im2col(const float* img, int B, int H, int W, void* out, int ld, int dtype, void* stream) {
-  if (!img || !out || H % 14 || W % 14 || ld < 588) return PF_ERR_ARG;
+  if (!img || !out) return pf_refuse("pf_patch_im2col", "null tensor");
+  if (pf_bad_dtype(dtype)) return pf_refuse("pf_patch_im2col", "bad dtype");
+  if (pf_misaligned(img, 4) || pf_misaligned(out, dtype == PF_DTYPE_BF16 ? 2 : 4)) return pf_refuse("pf_patch_im2col", "misaligned tensor");
+  if (B <= 0 || H <= 0 || W <= 0 || H % 14 || W % 14 || ld < 588) return pf_refuse("pf_patch_im2col", "B, H, W must be positive, H and W multiples of 14, ld >= 588");
   const long total = (long)B * (H / 14) * (W / 14) * ld;
   if (dtype == PF_DTYPE_BF16) hipLaunchKernelGGL(patch_im2col_kernel<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), img, B, H, W, (bf16_t*)out, ld);
   else hipLaunchKernelGGL(patch_im2col_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), img, B, H, W, (float*)out, ld);
@@ -1108,7 +1118,11 @@ extern "C" int pf_patch_im2col(const float* img, int B, int H, int W, void* out,
 
 extern "C" int pf_assemble_tokens(const void* emb, void* tokens, const float* cls, const float* pos, int B, int S, int D,
                                   int dtype, void* stream) {
-  if (!emb || !tokens || !cls || !pos) return PF_ERR_ARG;
+  if (!emb || !tokens || !cls || !pos) return pf_refuse("pf_assemble_tokens", "null tensor");
+  if (pf_bad_dtype(dtype)) return pf_refuse("pf_assemble_tokens", "bad dtype");
+  const unsigned el = dtype == PF_DTYPE_BF16 ? 2 : 4;
+  if (pf_misaligned(emb, el) || pf_misaligned(tokens, el) || pf_misaligned(cls, 4) || pf_misaligned(pos, 4)) return pf_refuse("pf_assemble_tokens", "misaligned tensor");
+  if (B <= 0 || S <= 0 || D <= 0 || D % 8) return pf_refuse("pf_assemble_tokens", "B, S must be positive, D a positive multiple of 8");
   const long total = (long)B * S * D;
   if (dtype == PF_DTYPE_BF16) hipLaunchKernelGGL(assemble_tokens_kernel<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), (const bf16_t*)emb, (bf16_t*)tokens, cls, pos, B, S, D);
   else hipLaunchKernelGGL(assemble_tokens_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), (const float*)emb, (float*)tokens, cls, pos, B, S, D);
@@ -1118,17 +1132,37 @@ extern "C" int pf_assemble_tokens(const void* emb, void* tokens, const float* cl
 extern "C" int pf_layernorm(const void* x, int x_ld, void* y, int y_ld, const float* g, const float* b, float eps,
                             int batches, int in_rows_per_batch, int in_row_offset, int out_rows_per_batch, int D,
                             int dtype, void* stream) {
-  if (!x || !y || !g || !b || D % 8 || D > 2048 || x_ld % 8 || y_ld % 8) return PF_ERR_ARG;
+  if (!x || !y || !g || !b) return pf_refuse("pf_layernorm", "null tensor");
+  if (pf_bad_dtype(dtype)) return pf_refuse("pf_layernorm", "bad dtype");
+  if (pf_misaligned(x, 16) || pf_misaligned(y, 16) || pf_misaligned(g, 4) || pf_misaligned(b, 4)) return pf_refuse("pf_layernorm", "misaligned tensor");
+  if (D <= 0 || D % 8 || D > 2048) return pf_refuse("pf_layernorm", "D must be a multiple of 8 in [8, 2048]");
+  if (x_ld % 8 || y_ld % 8 || x_ld < D || y_ld < D) return pf_refuse("pf_layernorm", "x_ld, y_ld must be multiples of 8 and >= D");
+  if (batches <= 0 || in_rows_per_batch <= 0 || out_rows_per_batch <= 0 || in_row_offset < 0 ||
+      (long)in_row_offset + out_rows_per_batch > in_rows_per_batch)
+    return pf_refuse("pf_layernorm", "the rows read must lie inside their batch");
   const long rows = (long)batches * out_rows_per_batch;
+  if (rows >= (1L << 31)) return pf_refuse("pf_layernorm", "too many rows");
   const int grid = (int)((rows + 3) / 4);
   if (dtype == PF_DTYPE_BF16) hipLaunchKernelGGL(layernorm_kernel<bf16_t>, dim3(grid), dim3(256), 0, ST(stream), (const bf16_t*)x, x_ld, (bf16_t*)y, y_ld, g, b, eps, batches, in_rows_per_batch, in_row_offset, out_rows_per_batch, D);
   else hipLaunchKernelGGL(layernorm_kernel<float>, dim3(grid), dim3(256), 0, ST(stream), (const float*)x, x_ld, (float*)y, y_ld, g, b, eps, batches, in_rows_per_batch, in_row_offset, out_rows_per_batch, D);
   return ok();
 }
 
+// the head-split buffers of pf_qkv_split / pf_vit_attention / pf_vit_attention_rpb_bf16: one block row per (batch, head)
+static const char* heads_envelope(int B, int S, int Sp, int Hh) {
+  if (B <= 0 || S <= 0 || Hh <= 0) return "B, S, Hh must be positive";
+  if (Sp % 64 || Sp < S) return "Sp must be a multiple of 64 and >= S";
+  if ((long)B * Hh > PF_GRID_YZ_MAX) return "B * Hh above 65535 (grid dimension y)";
+  if ((long)Hh * 192 >= (1L << 31)) return "too many heads";
+  return nullptr;
+}
+
 extern "C" int pf_qkv_split(const void* qkv, int B, int S, int Hh, void* q, void* k, void* vt, int Sp, float scale,
                             int dtype, void* stream) {
-  if (!qkv || !q || !k || !vt || Sp % 64 || Sp < S) return PF_ERR_ARG;
+  if (!qkv || !q || !k || !vt) return pf_refuse("pf_qkv_split", "null tensor");
+  if (pf_bad_dtype(dtype)) return pf_refuse("pf_qkv_split", "bad dtype");
+  if (pf_misaligned(qkv, 16) || pf_misaligned(q, 16) || pf_misaligned(k, 16) || pf_misaligned(vt, 16)) return pf_refuse("pf_qkv_split", "misaligned tensor");
+  if (const char* e = heads_envelope(B, S, Sp, Hh)) return pf_refuse("pf_qkv_split", e);
   dim3 grid((S + 63) / 64, B * Hh);
   if (dtype == PF_DTYPE_BF16) hipLaunchKernelGGL(qkv_split_kernel<bf16_t>, grid, dim3(256), 0, ST(stream), (const bf16_t*)qkv, B, S, Hh, (bf16_t*)q, (bf16_t*)k, (bf16_t*)vt, Sp, scale);
   else hipLaunchKernelGGL(qkv_split_kernel<float>, grid, dim3(256), 0, ST(stream), (const float*)qkv, B, S, Hh, (float*)q, (float*)k, (float*)vt, Sp, scale);
@@ -1137,7 +1171,11 @@ extern "C" int pf_qkv_split(const void* qkv, int B, int S, int Hh, void* q, void
 
 extern "C" int pf_vit_attention(const void* q, const void* k, const void* vt, void* out, int B, int S, int Sp, int Hh,
                                 int dtype, void* stream) {
-  if (!q || !k || !vt || !out || Sp % 64 || Sp < S) return PF_ERR_ARG;
+  if (!q || !k || !vt || !out) return pf_refuse("pf_vit_attention", "null tensor");
+  if (pf_bad_dtype(dtype)) return pf_refuse("pf_vit_attention", "bad dtype");
+  if (pf_misaligned(q, 16) || pf_misaligned(k, 16) || pf_misaligned(vt, 16) || pf_misaligned(out, dtype == PF_DTYPE_BF16 ? 8 : 16))
+    return pf_refuse("pf_vit_attention", "misaligned tensor");
+  if (const char* e = heads_envelope(B, S, Sp, Hh)) return pf_refuse("pf_vit_attention", e);
   dim3 grid((S + 63) / 64, B * Hh);
   static int old_attn = -1;
   if (old_attn < 0) { const char* e = getenv("PF_ATTN_OLD"); old_attn = (e && e[0] == '1') ? 1 : 0; }
@@ -1154,16 +1192,32 @@ extern "C" int pf_vit_attention_rpb_bf16_lds_bytes(int S, int th, int tw) {
 
 extern "C" int pf_vit_attention_rpb_bf16(const void* q, const void* k, const void* vt, void* out, int B, int S, int Sp, int Hh, const float* tab, int th,
                                          int tw, void* stream) {
-  if (!q || !k || !vt || !out || !tab || B <= 0 || Hh <= 0 || Sp % 64 || Sp < S) return PF_ERR_ARG;
-  if (th <= 0 || tw < 4 || (long)th * tw + 1 != S || S >= (1 << 20)) return PF_ERR_ARG;   // cls + the th x tw grid; the key-row division is exact below 2^20;
-  const int lds = pf_vit_attention_rpb_bf16_lds_bytes(S, th, tw);                          // a quad of keys crosses at most one grid row
+  if (!q || !k || !vt || !out || !tab) return pf_refuse("pf_vit_attention_rpb_bf16", "null tensor");
+  if (pf_misaligned(q, 16) || pf_misaligned(k, 16) || pf_misaligned(vt, 16) || pf_misaligned(out, 8) || pf_misaligned(tab, 4))
+    return pf_refuse("pf_vit_attention_rpb_bf16", "misaligned tensor");
+  if (const char* e = heads_envelope(B, S, Sp, Hh)) return pf_refuse("pf_vit_attention_rpb_bf16", e);
+  if (th <= 0 || tw < 4 || (long)th * tw + 1 != S || S >= (1 << 20))                         // cls + the th x tw grid; the key-row division is exact below 2^20;
+    return pf_refuse("pf_vit_attention_rpb_bf16", "S must be th * tw + 1 < 2^20 with tw >= 4");  // a quad of keys crosses at most one grid row
+  const int lds = pf_vit_attention_rpb_bf16_lds_bytes(S, th, tw);
   const int dyn = lds - 2 * 2 * 64 * 128;
-  if (lds > 160 * 1024) return PF_ERR_ARG;
-  static int attr_dyn = 0;
-  if (lds > 64 * 1024 && attr_dyn < dyn) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(vit_attention32_kernel<true, Rpb32Args>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn) != hipSuccess)
-      return PF_ERR_LAUNCH;
-    attr_dyn = dyn;
+  if (lds > 160 * 1024) return pf_refuse("pf_vit_attention_rpb_bf16", "the table slice does not fit the LDS");
+  // (the attribute belongs to a device and only ever grows: the size set so far per device, raised under a lock -- two threads with different
+  // window sizes cannot leave the smaller one behind)
+  static std::mutex attr_mu;
+  static std::atomic<int> attr_dyn[64];                       // (the other launchers opt in to ONE fixed size and keep a bit per device; this size grows with the
+  // window -- a bit cannot say "large enough", so the largest size set so far is kept per device, dev & 63 like those bitmasks)
+  if (lds > 64 * 1024) {
+    int dev = 0;
+    hipGetDevice(&dev);
+    std::atomic<int>& have = attr_dyn[dev & 63];
+    if (have.load(std::memory_order_acquire) < dyn) {         // the lock is taken only by a call that has to raise the size
+      std::lock_guard<std::mutex> hold(attr_mu);
+      if (have.load(std::memory_order_relaxed) < dyn) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(vit_attention32_kernel<true, Rpb32Args>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn) != hipSuccess)
+          return PF_ERR_LAUNCH;
+        have.store(dyn, std::memory_order_release);
+      }
+    }
   }
   hipLaunchKernelGGL((vit_attention32_kernel<true, Rpb32Args>), dim3((S + 127) / 128, B * Hh), dim3(256), dyn, ST(stream), (const bf16_t*)q, (const bf16_t*)k,
                      (const bf16_t*)vt, (bf16_t*)out, B, S, Sp, Hh, Rpb32Args{tab, th, tw});
@@ -1183,20 +1237,39 @@ static int attention_qkv(const void* qkv, void* out, long plane, int B, int S, i
   return ok();
 }
 
+// the QKV-row attention kernels: one block row per (batch, head), 16-byte loads of q / k / v rows
+static const char* qkv_envelope(int B, int S, int Hh) {
+  if (B <= 0 || S <= 0 || Hh <= 0) return "B, S, Hh must be positive";
+  if ((long)B * Hh > PF_GRID_YZ_MAX) return "B * Hh above 65535 (grid dimension y)";
+  if ((long)Hh * 192 >= (1L << 31)) return "too many heads";
+  return nullptr;
+}
+
 extern "C" int pf_vit_attention_qkv(const void* qkv, void* out, int B, int S, int Hh, int dtype, void* stream) {
-  if (!qkv || !out || B <= 0 || S <= 0 || Hh <= 0 || dtype != PF_DTYPE_F32) return PF_ERR_ARG;
+  if (!qkv || !out) return pf_refuse("pf_vit_attention_qkv", "null tensor");
+  if (dtype != PF_DTYPE_F32) return pf_refuse("pf_vit_attention_qkv", "float32 only");
+  if (pf_misaligned(qkv, 16) || pf_misaligned(out, 16)) return pf_refuse("pf_vit_attention_qkv", "misaligned tensor");
+  if (const char* e = qkv_envelope(B, S, Hh)) return pf_refuse("pf_vit_attention_qkv", e);
   return attention_qkv(qkv, out, 0, B, S, Hh, stream);
 }
 
 extern "C" int pf_vit_attention_qkv_split3(const void* qkv, void* out3, long plane, int kmajor, int B, int S, int Hh, void* stream) {
-  if (!qkv || !out3 || B <= 0 || S <= 0 || Hh <= 0 || plane < (long)B * S * Hh * 64) return PF_ERR_ARG;
+  if (!qkv || !out3) return pf_refuse("pf_vit_attention_qkv_split3", "null tensor");
+  if (pf_misaligned(qkv, 16) || pf_misaligned(out3, 8)) return pf_refuse("pf_vit_attention_qkv_split3", "misaligned tensor");
+  if (const char* e = qkv_envelope(B, S, Hh)) return pf_refuse("pf_vit_attention_qkv_split3", e);
+  if (plane < (long)B * S * Hh * 64 || plane % 4) return pf_refuse("pf_vit_attention_qkv_split3", "plane must hold B * S * Hh * 64 elements and be a multiple of 4");
   return attention_qkv(qkv, out3, plane, B, S, Hh, stream, kmajor ? (long)B * S : 0);
 }
 
 extern "C" int pf_layernorm_split3(const float* x, int x_ld, void* y3, int y_ld, long plane, int kmajor, const float* g, const float* b, float eps,
                                    long rows, int D, void* stream) {
-  if (!x || !y3 || !g || !b || D % 8 || D > 2048 || x_ld % 8 || y_ld % 8 || rows <= 0 || plane < (rows - 1) * y_ld + D) return PF_ERR_ARG;
-  if (kmajor && (D % 32 || y_ld != D)) return PF_ERR_ARG;                        // chunk-major planes are dense: [D/32][rows][32]
+  if (!x || !y3 || !g || !b) return pf_refuse("pf_layernorm_split3", "null tensor");
+  if (pf_misaligned(x, 16) || pf_misaligned(y3, 8) || pf_misaligned(g, 4) || pf_misaligned(b, 4)) return pf_refuse("pf_layernorm_split3", "misaligned tensor");
+  if (D <= 0 || D % 8 || D > 2048) return pf_refuse("pf_layernorm_split3", "D must be a multiple of 8 in [8, 2048]");
+  if (x_ld % 8 || y_ld % 8 || x_ld < D || y_ld < D) return pf_refuse("pf_layernorm_split3", "x_ld, y_ld must be multiples of 8 and >= D");
+  if (rows <= 0 || rows >= (1L << 31)) return pf_refuse("pf_layernorm_split3", "rows must be in [1, 2^31)");
+  if (plane < (rows - 1) * y_ld + D || plane % 4) return pf_refuse("pf_layernorm_split3", "plane must hold the rows and be a multiple of 4");
+  if (kmajor && (D % 32 || y_ld != D)) return pf_refuse("pf_layernorm_split3", "chunk-major planes are dense: D % 32 == 0, y_ld == D");      // [D/32][rows][32]
   hipLaunchKernelGGL(layernorm_split3_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ST(stream), x, x_ld, (bf16_t*)y3, y_ld, plane, g, b, eps, rows, D,
                      kmajor ? rows : 0L);
   return ok();
@@ -1204,14 +1277,23 @@ extern "C" int pf_layernorm_split3(const float* x, int x_ld, void* y3, int y_ld,
 
 extern "C" int pf_layernorm_f16x2(const float* x, int x_ld, void* y2, const int* in_exp, const float* g, const float* b, float eps, long rows, int D,
                                   void* stream) {
-  if (!x || !y2 || !in_exp || !g || !b || D % 32 || D > 2048 || x_ld % 8 || x_ld < D || rows <= 0) return PF_ERR_ARG;
+  if (!x || !y2 || !in_exp || !g || !b) return pf_refuse("pf_layernorm_f16x2", "null tensor");
+  if (pf_misaligned(x, 16) || pf_misaligned(y2, 16) || pf_misaligned(in_exp, 4) || pf_misaligned(g, 4) || pf_misaligned(b, 4))
+    return pf_refuse("pf_layernorm_f16x2", "misaligned tensor");
+  if (D <= 0 || D % 32 || D > 2048 || x_ld % 8 || x_ld < D) return pf_refuse("pf_layernorm_f16x2", "D must be a multiple of 32 in [32, 2048], x_ld a multiple of 8 >= D");
+  if (rows <= 0 || rows >= (1L << 31)) return pf_refuse("pf_layernorm_f16x2", "rows must be in [1, 2^31)");
   hipLaunchKernelGGL(layernorm_f16x2_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ST(stream), x, x_ld, (uint16_t*)y2, in_exp, g, b, eps, rows, D);
   return ok();
 }
 
 extern "C" int pf_vit_attention_split3(const void* qkv3, long plane_in, void* out3, long plane_out, int kmajor, int B, int S, int Hh, void* stream) {
-  if (!qkv3 || !out3 || B <= 0 || S <= 0 || Hh <= 0 || plane_in < (long)B * S * Hh * 192 || plane_out < (long)B * S * Hh * 64) return PF_ERR_ARG;
-  if (2 * plane_in + 64L * Hh * 192 + Hh * 192 >= (1L << 32)) return PF_ERR_ARG;          // (32-bit row offsets inside one 64-key tile, three planes)
+  if (!qkv3 || !out3) return pf_refuse("pf_vit_attention_split3", "null tensor");
+  if (pf_misaligned(qkv3, 16) || pf_misaligned(out3, 8)) return pf_refuse("pf_vit_attention_split3", "misaligned tensor");
+  if (const char* e = qkv_envelope(B, S, Hh)) return pf_refuse("pf_vit_attention_split3", e);
+  if (plane_in < (long)B * S * Hh * 192 || plane_out < (long)B * S * Hh * 64 || plane_in % 8 || plane_out % 4)
+    return pf_refuse("pf_vit_attention_split3", "planes must hold their rows (plane_in a multiple of 8, plane_out of 4)");
+  if (2 * plane_in + 64L * Hh * 192 + Hh * 192 >= (1L << 32))          // (32-bit row offsets inside one 64-key tile, three planes)
+    return pf_refuse("pf_vit_attention_split3", "plane_in too large for 32-bit tile offsets");
   const float qscale = 0.125f * 1.4426950408889634f;        // head_dim^-1/2 (attention.py:55) times log2(e): base-2 softmax
   hipLaunchKernelGGL(vit_attention_split3_kernel, dim3((S + 63) / 64, B * Hh), dim3(256), 0, ST(stream), (const bf16_t*)qkv3, plane_in, (bf16_t*)out3,
                      plane_out, B, S, Hh, qscale, kmajor ? (long)B * S : 0L);

@@ -14,6 +14,7 @@
 #include <climits>
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
+#include "pf_args.h"
 
 namespace {
 

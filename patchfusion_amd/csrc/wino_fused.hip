@@ -39,6 +39,7 @@
 #include <atomic>
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
+#include "pf_args.h"
 
 namespace {
 
@@ -554,18 +555,25 @@ int launch(const pf_conv_params* p, const void* up, int nnb, int gs, int shape, 
 }  // namespace
 
 extern "C" int pf_conv_winograd_fused_supported(const pf_conv_params* p) {
-  if (!p || p->dtype != PF_DTYPE_F32 || p->KH != 3 || p->KW != 3 || p->stride != 1 || p->pad != 1 || p->shuffle > 1 || p->scale) return 0;
-  if (p->OH != p->H || p->OW != p->W || p->Cin % 16 || p->Cin < 32 || p->Cout % 4 || p->Cout <= 0) return 0;
+  if (!p || p->dtype != PF_DTYPE_F32 || p->KH != 3 || p->KW != 3 || p->stride != 1 || p->pad != 1 || p->shuffle != 1 || p->scale) return 0;
+  if (p->B <= 0 || p->H <= 0 || p->W <= 0 || p->OH != p->H || p->OW != p->W || p->Cin % 16 || p->Cin < 32 || p->Cout % 4 || p->Cout <= 0) return 0;
   if (p->act != PF_ACT_NONE && p->act != PF_ACT_RELU) return 0;
   if (p->x_ld % 4 || p->y_ld % 4 || (p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) return 0;
+  if (p->x_ld < p->Cin || p->y_ld < p->Cout || (p->res && p->res_ld < p->Cout) || (p->res2 && p->res2_ld < p->Cout)) return 0;
+  // (float4 loads and stores; a null pointer counts as aligned here -- the launcher refuses null tensors itself)
+  if (pf_misaligned(p->x, 16) || pf_misaligned(p->y, 16) || pf_misaligned(p->bias, 16) || pf_misaligned(p->res, 16) || pf_misaligned(p->res2, 16)) return 0;
   const long pix = (long)p->B * p->H * p->W;
   if (pix * p->x_ld >= (1L << 31) || (long)p->B * ((p->H + 15) / 16) * ((p->W + 15) / 16) * ((p->Cout + 63) / 64) >= (1L << 31)) return 0;
   return 1;
 }
 
 extern "C" int pf_conv_winograd_fused(const pf_conv_params* p, const void* up, int nnb, int gs, void* stream) {
-  if (!p || !up || !p->x || !p->y) return PF_ERR_ARG;
-  if (!pf_conv_winograd_fused_supported(p) || nnb != (p->Cout + 63) / 64) return PF_ERR_ARG;
+  if (!p || !up || !p->x || !p->y) return pf_refuse("pf_conv_winograd_fused", "null tensor");
+  if (pf_misaligned(up, 16)) return pf_refuse("pf_conv_winograd_fused", "misaligned filters");
+  if (!pf_conv_winograd_fused_supported(p)) return pf_refuse("pf_conv_winograd_fused", "the layer does not qualify (pf_conv_winograd_fused_supported)");
+  if (nnb != (p->Cout + 63) / 64) return pf_refuse("pf_conv_winograd_fused", "nnb must be ceil(Cout / 64)");
+  if (gs < 0 || (((gs >> 16) & 0xf) != 0 && ((gs >> 16) & 0xf) != 4 && ((gs >> 16) & 0xf) != 8))
+    return pf_refuse("pf_conv_winograd_fused", "gs must be >= 0 with a forced super-tile width of 0, 4 or 8");
   // gs: low 16 bits = super-tiles per block group; bits 16-19 = forced super-tile shape (8 | 4, 0 = automatic), bits 20.. = the
   // timing-decomposition switches of WF::dbg -- tuning aids
   return launch(p, up, nnb, gs & 0xffff, (gs >> 16) & 0xf, gs >> 20, reinterpret_cast<hipStream_t>(stream));

@@ -14,6 +14,7 @@
 #include <mutex>
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
+#include "pf_args.h"
 
 // csrc/wino_f16x2.hip
 namespace pf_f16x2 {
@@ -436,12 +437,35 @@ int run_f16x2(const pf_conv_params* p, const float* U, int u_rows, void* V2, flo
   return PF_OK;
 }
 
+// What every three-step Winograd entry point refuses in `p` (nullptr = accepted): a null p / x / y; tensors (x, y, bias, res, res2) off a 16-byte
+// boundary; anything but a float32 3 x 3 / stride 1 / pad 1 layer without pixel shuffle (shuffle != 1) or scale; B, H, W not positive or OH, OW not
+// H, W; Cin not a positive multiple of 32, Cout of 8; x_ld / y_ld / res_ld / res2_ld not multiples of 4 or below the channels they hold; an
+// activation other than NONE / RELU; 2^31 or more pixels.
+const char* wino_layer_refusal(const pf_conv_params* p) {
+  if (!p || !p->x || !p->y) return "null tensor";
+  if (pf_misaligned(p->x, 16) || pf_misaligned(p->y, 16) || pf_misaligned(p->bias, 16) || pf_misaligned(p->res, 16) || pf_misaligned(p->res2, 16))
+    return "misaligned tensor";
+  if (p->dtype != PF_DTYPE_F32 || p->KH != 3 || p->KW != 3 || p->stride != 1 || p->pad != 1 || p->shuffle != 1 || p->scale)
+    return "float32 3x3 / stride 1 / pad 1 layers without shuffle or scale only";
+  if (p->B <= 0 || p->H <= 0 || p->W <= 0 || p->OH != p->H || p->OW != p->W) return "B, H, W must be positive, OH == H, OW == W";
+  if (p->Cin <= 0 || p->Cout <= 0 || p->Cin % 32 || p->Cout % 8) return "Cin must be a positive multiple of 32, Cout of 8";
+  if (p->x_ld % 4 || p->x_ld < p->Cin || p->y_ld % 4 || p->y_ld < p->Cout) return "x_ld, y_ld must be multiples of 4 and hold the channels";
+  if ((p->res && (p->res_ld % 4 || p->res_ld < p->Cout)) || (p->res2 && (p->res2_ld % 4 || p->res2_ld < p->Cout)))
+    return "residual ld must be a multiple of 4 and >= Cout";
+  if (p->act != PF_ACT_NONE && p->act != PF_ACT_RELU) return "act must be NONE or RELU";
+  if ((long)p->B * p->H * p->W >= (1L << 31)) return "too many pixels";
+  return nullptr;
+}
+const char* window_refusal(long window) { return window < 0 || (window > 0 && window % 8) ? "window must be 0 or a positive multiple of 8" : nullptr; }
+
+inline const char* f16x2_why(const pf_conv_params* p) {
+  const char* e = wino_layer_refusal(p);
+  return e ? e : "window / u_rows / u_kpad / Cin > 8192";
+}
+
 // the argument rules of pf_conv_winograd_split3_windowed (U = PackedConv.wino_u: float32 [36][u_rows][Cin])
 bool f16x2_args_ok(const pf_conv_params* p, int u_rows, int u_kpad, long window) {
-  if (!p || !p->x || !p->y || window < 0 || (window > 0 && window % 8)) return false;
-  if (p->dtype != PF_DTYPE_F32 || p->KH != 3 || p->KW != 3 || p->stride != 1 || p->pad != 1 || p->shuffle > 1 || p->scale) return false;
-  if (p->OH != p->H || p->OW != p->W || p->Cin % 32 || p->Cout % 8 || p->Cin <= 0 || p->Cout <= 0 || p->Cin > 8192) return false;
-  if (p->act != PF_ACT_NONE && p->act != PF_ACT_RELU) return false;
+  if (wino_layer_refusal(p) || window_refusal(window) || p->Cin > 8192) return false;
   return u_rows >= p->Cout && u_rows % 16 == 0 && u_kpad == p->Cin;
 }
 
@@ -468,7 +492,9 @@ extern "C" int pf_conv_winograd_f16x2_supported_ex(const pf_conv_params* p, int 
 
 extern "C" int pf_conv_winograd_f16x2_windowed(const pf_conv_params* p, const void* U, int u_rows, int u_kpad, void* V2, void* M, void* scratch,
                                                long window, void* stream) {
-  if (!U || !V2 || !M || !scratch || !f16x2_args_ok(p, u_rows, u_kpad, window)) return PF_ERR_ARG;
+  if (!U || !V2 || !M || !scratch) return pf_refuse("pf_conv_winograd_f16x2_windowed", "null pointer");
+  if (pf_misaligned(U, 16) || pf_misaligned(V2, 16) || pf_misaligned(M, 16) || pf_misaligned(scratch, 16)) return pf_refuse("pf_conv_winograd_f16x2_windowed", "misaligned pointer");
+  if (!f16x2_args_ok(p, u_rows, u_kpad, window)) return pf_refuse("pf_conv_winograd_f16x2_windowed", f16x2_why(p));
   return run_f16x2(p, static_cast<const float*>(U), u_rows, V2, static_cast<float*>(M), scratch, window, ST(stream));
 }
 
@@ -477,53 +503,57 @@ extern "C" int pf_conv_winograd_f16x2_windowed(const pf_conv_params* p, const vo
 // maxima of y (uint32 [Cout]; of max(y, 0) when cmax_out_relu), or null.  cmax_out must not be the buffer cmax_in points to.
 extern "C" int pf_conv_winograd_f16x2_windowed_ex(const pf_conv_params* p, const void* U, int u_rows, int u_kpad, void* V2, void* M, void* scratch,
                                                   long window, const void* cmax_in, void* cmax_out, int cmax_out_relu, void* stream) {
-  if (!U || !V2 || !M || !scratch || !f16x2_args_ok(p, u_rows, u_kpad, window) || (cmax_in && cmax_in == cmax_out)) return PF_ERR_ARG;
+  if (!U || !V2 || !M || !scratch) return pf_refuse("pf_conv_winograd_f16x2_windowed_ex", "null pointer");
+  if (pf_misaligned(U, 16) || pf_misaligned(V2, 16) || pf_misaligned(M, 16) || pf_misaligned(scratch, 16) || pf_misaligned(cmax_in, 4) || pf_misaligned(cmax_out, 4))
+    return pf_refuse("pf_conv_winograd_f16x2_windowed_ex", "misaligned pointer");
+  if (!f16x2_args_ok(p, u_rows, u_kpad, window)) return pf_refuse("pf_conv_winograd_f16x2_windowed_ex", f16x2_why(p));
+  if (cmax_in && cmax_in == cmax_out) return pf_refuse("pf_conv_winograd_f16x2_windowed_ex", "cmax_out must not be cmax_in");
   return run_f16x2(p, static_cast<const float*>(U), u_rows, V2, static_cast<float*>(M), scratch, window, ST(stream),
                    static_cast<const unsigned*>(cmax_in), static_cast<unsigned*>(cmax_out), cmax_out_relu);
 }
 
 extern "C" int pf_wino_absmax(const void* x, int x_ld, long P, int C, int relu_in, void* cmax, void* stream) {
-  if (!x || !cmax || P <= 0 || C <= 0 || C % 4 || x_ld < C || x_ld % 4) return PF_ERR_ARG;
+  if (!x || !cmax || pf_misaligned(x, 16) || pf_misaligned(cmax, 4)) return pf_refuse("pf_wino_absmax", "null or misaligned pointer");
+  if (P <= 0 || C <= 0 || C % 4 || x_ld < C || x_ld % 4) return pf_refuse("pf_wino_absmax", "P must be positive, C a positive multiple of 4, x_ld a multiple of 4 >= C");
   return pf_f16x2::launch_absmax(static_cast<const float*>(x), x_ld, P, C, relu_in, static_cast<unsigned*>(cmax), ST(stream));
 }
 
 extern "C" int pf_conv_winograd_split3(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, void* V3, void* M, void* stream) {
-  if (!p || !U3 || !V3 || !M || !p->x || !p->y) return PF_ERR_ARG;
-  if (p->dtype != PF_DTYPE_F32 || p->KH != 3 || p->KW != 3 || p->stride != 1 || p->pad != 1 || p->shuffle > 1 || p->scale) return PF_ERR_ARG;
-  if (p->OH != p->H || p->OW != p->W || p->Cin % 32 || p->Cout % 8 || p->Cin <= 0 || p->Cout <= 0) return PF_ERR_ARG;
-  if (p->act != PF_ACT_NONE && p->act != PF_ACT_RELU) return PF_ERR_ARG;
-  if (u_rows < p->Cout || u_kpad != p->Cin) return PF_ERR_ARG;       // (chunk-major planes are dense in K)
+  if (!U3 || !V3 || !M) return pf_refuse("pf_conv_winograd_split3", "null pointer");
+  if (pf_misaligned(U3, 16) || pf_misaligned(V3, 16) || pf_misaligned(M, 16)) return pf_refuse("pf_conv_winograd_split3", "misaligned pointer");
+  if (const char* e = wino_layer_refusal(p)) return pf_refuse("pf_conv_winograd_split3", e);
+  if (u_rows < p->Cout || u_kpad != p->Cin) return pf_refuse("pf_conv_winograd_split3", "u_rows must be >= Cout, u_kpad == Cin");       // (chunk-major planes are dense in K)
   return run_split3(p, U3, u_rows, u_kpad, V3, static_cast<float*>(M), 0, ST(stream));
 }
 
 // the same layer `window` Winograd tiles at a time (0 / >= all tiles: one window): V3 / M are arenas for ONE window -- 3 x 36 x ceil8(window) x Cin bf16
 // and 36 x window x Cout float32.  Identical results for every window (tiles are independent).
 extern "C" int pf_conv_winograd_split3_windowed(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, void* V3, void* M, long window, void* stream) {
-  if (!p || !U3 || !V3 || !M || !p->x || !p->y || window < 0 || (window > 0 && window % 8)) return PF_ERR_ARG;
-  if (p->dtype != PF_DTYPE_F32 || p->KH != 3 || p->KW != 3 || p->stride != 1 || p->pad != 1 || p->shuffle > 1 || p->scale) return PF_ERR_ARG;
-  if (p->OH != p->H || p->OW != p->W || p->Cin % 32 || p->Cout % 8 || p->Cin <= 0 || p->Cout <= 0) return PF_ERR_ARG;
-  if (p->act != PF_ACT_NONE && p->act != PF_ACT_RELU) return PF_ERR_ARG;
-  if (u_rows < p->Cout || u_kpad != p->Cin) return PF_ERR_ARG;
+  if (!U3 || !V3 || !M) return pf_refuse("pf_conv_winograd_split3_windowed", "null pointer");
+  if (pf_misaligned(U3, 16) || pf_misaligned(V3, 16) || pf_misaligned(M, 16)) return pf_refuse("pf_conv_winograd_split3_windowed", "misaligned pointer");
+  if (const char* e = wino_layer_refusal(p)) return pf_refuse("pf_conv_winograd_split3_windowed", e);
+  if (const char* e = window_refusal(window)) return pf_refuse("pf_conv_winograd_split3_windowed", e);
+  if (u_rows < p->Cout || u_kpad != p->Cin) return pf_refuse("pf_conv_winograd_split3_windowed", "u_rows must be >= Cout, u_kpad == Cin");
   return run_split3(p, U3, u_rows, u_kpad, V3, static_cast<float*>(M), window, ST(stream));
 }
 
 // the same layer as the PRODUCER of an fp16x2 layer's range pass: its output transform merges the channel maxima of y into cmax_out (uint32 [Cout])
 extern "C" int pf_conv_winograd_split3_windowed_ex(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, void* V3, void* M, long window,
                                                    void* cmax_out, int cmax_out_relu, void* stream) {
-  if (!p || !U3 || !V3 || !M || !p->x || !p->y || window < 0 || (window > 0 && window % 8)) return PF_ERR_ARG;
-  if (p->dtype != PF_DTYPE_F32 || p->KH != 3 || p->KW != 3 || p->stride != 1 || p->pad != 1 || p->shuffle > 1 || p->scale) return PF_ERR_ARG;
-  if (p->OH != p->H || p->OW != p->W || p->Cin % 32 || p->Cout % 8 || p->Cin <= 0 || p->Cout <= 0) return PF_ERR_ARG;
-  if (p->act != PF_ACT_NONE && p->act != PF_ACT_RELU) return PF_ERR_ARG;
-  if (u_rows < p->Cout || u_kpad != p->Cin) return PF_ERR_ARG;
+  if (!U3 || !V3 || !M) return pf_refuse("pf_conv_winograd_split3_windowed_ex", "null pointer");
+  if (pf_misaligned(U3, 16) || pf_misaligned(V3, 16) || pf_misaligned(M, 16) || pf_misaligned(cmax_out, 4)) return pf_refuse("pf_conv_winograd_split3_windowed_ex", "misaligned pointer");
+  if (const char* e = wino_layer_refusal(p)) return pf_refuse("pf_conv_winograd_split3_windowed_ex", e);
+  if (const char* e = window_refusal(window)) return pf_refuse("pf_conv_winograd_split3_windowed_ex", e);
+  if (u_rows < p->Cout || u_kpad != p->Cin) return pf_refuse("pf_conv_winograd_split3_windowed_ex", "u_rows must be >= Cout, u_kpad == Cin");
   return run_split3(p, U3, u_rows, u_kpad, V3, static_cast<float*>(M), window, ST(stream), static_cast<unsigned*>(cmax_out), cmax_out_relu);
 }
 
 extern "C" int pf_conv_winograd(const pf_conv_params* p, int m, const void* U, int u_rows, int u_kpad, void* V, void* M, void* stream) {
-  if (!p || !U || !V || !M || !p->x || !p->y) return PF_ERR_ARG;
-  if (p->dtype != PF_DTYPE_F32 || p->KH != 3 || p->KW != 3 || p->stride != 1 || p->pad != 1 || p->shuffle > 1 || p->scale) return PF_ERR_ARG;
-  if (p->OH != p->H || p->OW != p->W || p->Cin % 32 || p->Cout % 8 || p->Cin <= 0 || p->Cout <= 0) return PF_ERR_ARG;
-  if (p->act != PF_ACT_NONE && p->act != PF_ACT_RELU) return PF_ERR_ARG;
-  if (u_rows < p->Cout || u_kpad < p->Cin || u_kpad % 32) return PF_ERR_ARG;
+  if (!U || !V || !M) return pf_refuse("pf_conv_winograd", "null pointer");
+  if (pf_misaligned(U, 16) || pf_misaligned(V, 16) || pf_misaligned(M, 16)) return pf_refuse("pf_conv_winograd", "misaligned pointer");
+  if (const char* e = wino_layer_refusal(p)) return pf_refuse("pf_conv_winograd", e);
+  if (m != 2 && m != 4) return pf_refuse("pf_conv_winograd", "m must be 2 or 4");
+  if (u_rows < p->Cout || u_kpad < p->Cin || u_kpad % 32) return pf_refuse("pf_conv_winograd", "u_rows must be >= Cout, u_kpad a multiple of 32 >= Cin");
   if (m == 2) return run<2>(p, static_cast<const float*>(U), u_rows, u_kpad, static_cast<float*>(V), static_cast<float*>(M), ST(stream));
   if (m == 4) return run<4>(p, static_cast<const float*>(U), u_rows, u_kpad, static_cast<float*>(V), static_cast<float*>(M), ST(stream));
   return PF_ERR_ARG;
