@@ -243,6 +243,23 @@ int pf_gemm_split3_ex(const pf_conv_params* p, int grid_cap, void* stream);
 #define PF_S3_ROUTE_TILE160 4 /* pf_gemm_f16x2_route only: the persistent 160 x 256 fp16x2 form */
 /* pf_gemm_split3_route: Answers -1 for a null p or cus <= 0. */
 int pf_gemm_split3_route(const pf_conv_params* p, int cus);
+/* how many blocks a persistent GEMM launches for `total` tiles on a chip of `cus` compute units (no launch, no GPU needed: the grid rule for
+ * host-side tests).  One block per CU, at most `total`, rounded down to a multiple of 8.  `policy` = the knobs the launcher honours, PF_GRID_CAP
+ * (grid_cap > 0 caps the CUs) | PF_GRID_ENV (PF_S3_GRID, read per call, replaces CUs and cap), plus exactly one rule for fewer than 8 blocks:
+ *   launcher                                  policy
+ *   pf_gemm_split3, 128 and 192 tiles         PF_GRID_CAP | PF_GRID_ENV | PF_GRID_FALLBACK
+ *   pf_gemm_f16x2_points                      PF_GRID_CAP | PF_GRID_REFUSE
+ *   pf_gemm_f16x2, 192 x 192 tiles            PF_GRID_FLOOR8
+ *   pf_gemm_f16x2, 160 x 256 tiles            PF_GRID_ENV | PF_GRID_FLOOR8
+ *   pf_gemm_f16x2_points128                   PF_GRID_CAP | PF_GRID_FLOOR8
+ * Answers the grid; 0 where the launcher falls back to its one-tile kernel; -1 where it refuses (also total > 2^31 - 1). */
+#define PF_GRID_CAP 1
+#define PF_GRID_ENV 2
+#define PF_GRID_FLOOR8 4   /* fewer than 8 blocks: 8 anyway */
+#define PF_GRID_FALLBACK 8 /* fewer than 8 blocks: the one-tile kernel runs the call */
+#define PF_GRID_REFUSE 16  /* fewer than 8 blocks: PF_ERR_ARG */
+/* pf_persist_grid: Answers -1 for cus <= 0, total <= 0, policy bits outside PF_GRID_* or not exactly one of FLOOR8 / FALLBACK / REFUSE. */
+int pf_persist_grid(int cus, int grid_cap, long total, int policy);
 /* pf_gemm_split3_timed: Refused (PF_ERR_ARG): as pf_gemm_split3, and a null ms or iters <= 0. */
 int pf_gemm_split3_timed(const pf_conv_params* p, int iters, float* ms, void* stream);
 /* A plain bf16 linear layer (x [M][x_ld] bf16, w from packing.pack_conv, bf16 residuals / output, float32 output when out_f32) through the same

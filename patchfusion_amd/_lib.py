@@ -199,7 +199,7 @@ SIGNATURES = {
 NON_STATUS = ("pf_last_error", "pf_version", "pf_percentile_workspace_bytes", "pf_conv_winograd_fused_supported", "pf_gemm_split3_route",
               "pf_gemm_f16x2_points_route", "pf_gemm_f16x2_points_route_ex", "pf_gemm_f16x2_route", "pf_conv_winograd_f16x2_supported_ex",
               "pf_wino_f16x2_scratch_bytes", "pf_conv_winograd_f16x2_supported", "pf_vit_attention_rpb_bf16_lds_bytes",
-              "pf_conv_last_variant", "pf_pngd_par_window")   # entry points that do not return a status
+              "pf_conv_last_variant", "pf_pngd_par_window", "pf_persist_grid")   # entry points that do not return a status
 
 _lib = None
 
@@ -234,6 +234,8 @@ def load():
     lib.pf_gemm_f16x2_points_route_ex.argtypes = [C.POINTER(ConvParams), ci, ci]
     lib.pf_gemm_f16x2_route.restype = ci                       # PF_S3_ROUTE_PERSIST192 / TILE160 (or -1): the tile form of an fp16x2 linear
     lib.pf_gemm_f16x2_route.argtypes = [C.POINTER(ConvParams), ci]
+    lib.pf_persist_grid.restype = ci                           # blocks of a persistent GEMM (0 = one-tile kernel, -1 = refused), not a status
+    lib.pf_persist_grid.argtypes = [ci, ci, C.c_long, ci]
     lib.pf_conv_winograd_f16x2_supported_ex.restype = ci              # 1 / 0, not a status
     lib.pf_conv_winograd_f16x2_supported_ex.argtypes = [C.POINTER(ConvParams), ci, ci, C.c_long, ci]
     lib.pf_wino_f16x2_scratch_bytes.restype = C.c_long                 # bytes, not a status

@@ -28,6 +28,7 @@
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
 #include "pf_args.h"
+#include "pf_launch.h"
 
 #include <atomic>
 #include <mutex>
@@ -1274,22 +1275,17 @@ extern "C" int pf_vit_attention_split3_v2(const void* qkv3, long plane_in, void*
   if (const char* e = getenv("PF_ATTN_DBG")) dbg = atoi(e);
   if (const char* e = getenv("PF_ATTN_LDS")) lds2 = ldsp = atoi(e);      // (bytes of dynamic LDS requested: > 80 KiB leaves ONE block per CU)
 #endif
-  // (the attribute belongs to a device: one bit per device, as in conv1x1_split3.hip -- a process that drives several GPUs sets it on each)
-  static std::atomic<unsigned long long> attr_done{0};
+  static std::atomic<unsigned long long> v2_done{0}, pipe_done{0};       // (the two schedules opt in to their own sizes)
 #ifdef PF_ATTN_DBG
   static std::atomic<int> attr_lds{0};
-  if (attr_lds.exchange(lds2) != lds2) attr_done.store(0, std::memory_order_release);
-#endif
-  int dev = 0;
-  hipGetDevice(&dev);
-  const unsigned long long dev_bit = 1ull << (dev & 63);
-  if (!(attr_done.load(std::memory_order_acquire) & dev_bit)) {
-    const void* ks[3] = {reinterpret_cast<const void*>(vit_attention_split3_v2_kernel<1>), reinterpret_cast<const void*>(vit_attention_split3_v2_kernel<2>),
-                         reinterpret_cast<const void*>(vit_attention_split3_pipe_kernel)};
-    for (int i = 0; i < 3; ++i)
-      if (hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, i < 2 ? lds2 : ldsp) != hipSuccess) return PF_ERR_LAUNCH;
-    attr_done.fetch_or(dev_bit, std::memory_order_release);
+  if (attr_lds.exchange(lds2) != lds2) {
+    v2_done.store(0, std::memory_order_release);
+    pipe_done.store(0, std::memory_order_release);
   }
+#endif
+  if (schedule == 1 ? !pf_ensure_dynamic_lds(v2_done, lds2, vit_attention_split3_v2_kernel<1>, vit_attention_split3_v2_kernel<2>)
+                    : !pf_ensure_dynamic_lds(pipe_done, ldsp, vit_attention_split3_pipe_kernel))
+    return PF_ERR_LAUNCH;
   int qw = queries_per_wave;
   if (schedule != 1) qw = 32;                                 // the pipelined kernel: a wave = the 32 columns of its accumulator tiles
   if (qw == 0) qw = (long)((S + 127) / 128) * B * Hh >= 512 ? 32 : 16;
@@ -1318,14 +1314,7 @@ extern "C" int pf_vit_attention_f16x2(const void* qkv2, long plane_in, const int
   if (pf_misaligned(qkv2, 16) || pf_misaligned(out2, 8) || pf_misaligned(qk_exp, 4) || pf_misaligned(v_exp3, 16)) return pf_refuse("pf_vit_attention_f16x2", "misaligned tensor");
   if (const char* e = attn_planes(B, S, Hh, plane_in, plane_out)) return pf_refuse("pf_vit_attention_f16x2", e);
   static std::atomic<unsigned long long> attr_done{0};
-  int dev = 0;
-  hipGetDevice(&dev);
-  const unsigned long long dev_bit = 1ull << (dev & 63);
-  if (!(attr_done.load(std::memory_order_acquire) & dev_bit)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(vit_attention_f16x2_pipe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PIPE_H_LDS) != hipSuccess)
-      return PF_ERR_LAUNCH;
-    attr_done.fetch_or(dev_bit, std::memory_order_release);
-  }
+  if (!pf_ensure_dynamic_lds(attr_done, PIPE_H_LDS, vit_attention_f16x2_pipe_kernel)) return PF_ERR_LAUNCH;
   const float qscale = 0.125f * 1.4426950408889634f;        // head_dim^-1/2 times log2(e); the head exponents join it in the kernel
   const int n_qb = (S + 127) / 128;
   hipLaunchKernelGGL(vit_attention_f16x2_pipe_kernel, dim3(n_qb * B * Hh), dim3(256), PIPE_H_LDS, reinterpret_cast<hipStream_t>(stream),

@@ -33,6 +33,7 @@
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
 #include "pf_args.h"
+#include "pf_launch.h"
 
 namespace {
 
@@ -298,14 +299,13 @@ extern "C" int pf_conv1x1_split3(const pf_conv_params* p, const void* w3, int w3
   // PF_C1_BM = 64 | 128 forces a token tile (A/B, tests); default 64 (two blocks per CU).  PF_C1_PERSIST=0: one tile per block (A/B, tests).
   static const int force = [] { const char* e = getenv("PF_C1_BM"); return e ? atoi(e) : 0; }();
   static const bool persist = [] { const char* e = getenv("PF_C1_PERSIST"); return !(e && e[0] == '0'); }();
-  static const int cus = [] { int d = 0, n = 0; hipGetDevice(&d); hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
   const int bm = force == 128 ? 128 : 64;
   const int mt = (int)((M + bm - 1) / bm), nt = (p->Cout + BN - 1) / BN;
   if ((long)mt * nt >= (1L << 31)) return pf_refuse("pf_conv1x1_split3", "argument outside the envelope (include/pf_hip.h)");
   // the grid: nslots token-tile slots per channel tile; persistent = as many blocks as are resident at once (two per CU at BM = 64, one at 128)
   int nslots = mt;
   if (persist) {
-    const int resident = (bm == 64 ? 2 : 1) * cus;
+    const int resident = (bm == 64 ? 2 : 1) * pf_cu_count();
     nslots = resident / nt > 0 ? resident / nt : 1;
     if (nslots > mt) nslots = mt;
   }
@@ -314,22 +314,17 @@ extern "C" int pf_conv1x1_split3(const pf_conv_params* p, const void* w3, int w3
     if (v > 0) nslots = v < mt ? v : mt;
   }
   constexpr int lds64 = 3 * 64 * 128 + 2 * WSTAGE, lds128 = 3 * 128 * 128 + 2 * WSTAGE;
-  // (the attribute belongs to a device: one bit per device, as in gemm_split3.hip -- a process that drives several GPUs sets it on each)
-  static std::atomic<unsigned long long> attr_done{0};
-  int dev = 0;
-  hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_split3_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, lds64) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_split3_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, lds128) != hipSuccess)
-      return PF_ERR_LAUNCH;
-    attr_done.fetch_or(bit, std::memory_order_release);
-  }
+  static std::atomic<unsigned long long> done64{0}, done128{0};    // (each token tile opts in to its own size)
   const long w_bstride = (long)(p->Cin / 32) * w3_rows * 32;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bf16_t* w = static_cast<const bf16_t*>(w3);
   const dim3 grid((unsigned)(nslots * nt));
-  if (bm == 128) hipLaunchKernelGGL(conv1x1_split3_kernel<128>, grid, dim3(512), lds128, st, *p, w, w3_rows, w_bstride, mt, nt, nslots);
-  else hipLaunchKernelGGL(conv1x1_split3_kernel<64>, grid, dim3(256), lds64, st, *p, w, w3_rows, w_bstride, mt, nt, nslots);
+  if (bm == 64) {
+    if (!pf_ensure_dynamic_lds(done64, lds64, conv1x1_split3_kernel<64>)) return PF_ERR_LAUNCH;
+    hipLaunchKernelGGL(conv1x1_split3_kernel<64>, grid, dim3(256), lds64, st, *p, w, w3_rows, w_bstride, mt, nt, nslots);
+  } else {
+    if (!pf_ensure_dynamic_lds(done128, lds128, conv1x1_split3_kernel<128>)) return PF_ERR_LAUNCH;
+    hipLaunchKernelGGL(conv1x1_split3_kernel<128>, grid, dim3(512), lds128, st, *p, w, w3_rows, w_bstride, mt, nt, nslots);
+  }
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
 }

@@ -29,6 +29,7 @@
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
 #include "pf_args.h"
+#include "pf_launch.h"
 
 namespace {
 
@@ -318,23 +319,13 @@ __global__ __launch_bounds__(512) void gemm_f16x2_persist160_kernel(const pf_con
 int pf_launch_f16x2_tile160(const pf_conv_params& p, int cus, hipStream_t st) {
   constexpr int smem = 3 * 2 * (160 + 256) * 64;
   static std::atomic<unsigned long long> done{0};
-  int dev = 0;
-  hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(done.load(std::memory_order_acquire) & bit)) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16x2_persist160_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    done.fetch_or(bit, std::memory_order_release);
-  }
   if (!p.out_f32 || (p.korder & 48) || p.batch > 1) return PF_ERR_ARG;
   const long M = (long)p.B * p.OH * p.OW;
   const int mt = (int)((M + 159) / 160), nt = (p.Cout + 255) / 256;
   const long total = (long)mt * nt;
-  int grid = cus;
-  if (const char* s = getenv("PF_S3_GRID")) grid = atoi(s);              // (tests: fewer blocks than CUs = more tiles per block; read per call)
-  if (grid > total) grid = (int)total;
-  grid &= ~7;                                                            // (8 XCDs on gfx950: the walk gives every XCD a contiguous tile range)
-  if (grid < 8) grid = 8;
-  if (total > 0x7fffffffL) return PF_ERR_ARG;
+  const int grid = pf_launch::persist_grid(cus, 0, total, PF_GRID_ENV | PF_GRID_FLOOR8);
+  if (grid < 0) return PF_ERR_ARG;
+  if (!pf_ensure_dynamic_lds(done, smem, gemm_f16x2_persist160_kernel)) return PF_ERR_LAUNCH;
   hipLaunchKernelGGL(gemm_f16x2_persist160_kernel, dim3((unsigned)grid), dim3(512), smem, st, p, mt, nt, (int)total);
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
 }

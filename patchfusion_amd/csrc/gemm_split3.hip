@@ -30,6 +30,7 @@
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
 #include "pf_args.h"
+#include "pf_launch.h"
 
 namespace {
 
@@ -1096,19 +1097,6 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
 }
 
 thread_local char g_err[200] = {0};
-constexpr int PF_ERR_FALLBACK = -100;     // internal: the persistent launch is not legal for this grid, use the one-tile kernel
-
-int cu_count() {
-  static std::atomic<int> cus[64];
-  int dev = 0;
-  hipGetDevice(&dev);
-  int c = cus[dev & 63].load(std::memory_order_relaxed);
-  if (c <= 0) {
-    if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0) c = 256;
-    cus[dev & 63].store(c, std::memory_order_relaxed);
-  }
-  return c;
-}
 
 // Tile order of the persistent kernels inside a transform point: the ~32 tiles an XCD works on at once are consecutive in the order, and they
 // should be a patch whose X and W panels are shared through that XCD's L2.  nt (channel tiles) dividing 32: gm = 32 / nt token tiles x all channel
@@ -1131,25 +1119,13 @@ int tile_group(int nt) {
 int launch_persist(const pf_conv_params& p, hipStream_t st, int grid_cap) {
   constexpr int smem = 3 * 3 * (128 + 128) * 64;
   static std::atomic<unsigned long long> done{0};
-  int dev = 0;
-  hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(done.load(std::memory_order_acquire) & bit)) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3_persist_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3_persist_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    done.fetch_or(bit, std::memory_order_release);
-  }
   const long M = (long)p.B * p.OH * p.OW;
   const int mt = (int)((M + 127) / 128), nt = (p.Cout + 127) / 128;
   const long total = (long)mt * nt * (p.batch > 1 ? p.batch : 1);
   const int gm = tile_group(nt);
-  int grid = cu_count();
-  if (grid_cap > 0 && grid_cap < grid) grid = grid_cap;                  // (pf_gemm_split3_ex: leave CUs to a concurrent HBM-bound stream)
-  if (const char* s = getenv("PF_S3_GRID")) grid = atoi(s);              // (tests: fewer blocks than CUs = more tiles per block; read per call)
-  if (grid > total) grid = (int)total;
-  grid &= ~7;                                                            // (8 XCDs on gfx950: the walk gives every XCD a contiguous tile range)
-  if (total > 0x7fffffffL) return PF_ERR_ARG;
-  if (grid < 8) return PF_ERR_FALLBACK;                                  // (a PF_S3_GRID below 8 / not a number: the caller runs the one-tile kernel)
+  const int grid = pf_launch::persist_grid(pf_cu_count(), grid_cap, total, PF_GRID_CAP | PF_GRID_ENV | PF_GRID_FALLBACK);
+  if (grid < 0) return grid == PF_ERR_FALLBACK ? grid : PF_ERR_ARG;      // (fallback: the caller runs the one-tile kernel)
+  if (!pf_ensure_dynamic_lds(done, smem, gemm_split3_persist_kernel<true>, gemm_split3_persist_kernel<false>)) return PF_ERR_LAUNCH;
 #ifdef PF_S3_DBG
   const bool bare = !p.bias && !p.scale && !p.res && p.act == PF_ACT_NONE && p.out_f32;          // (res2 = the timeline buffer)
 #else
@@ -1164,27 +1140,15 @@ int launch_persist(const pf_conv_params& p, hipStream_t st, int grid_cap) {
 int launch_persist192(const pf_conv_params& p, hipStream_t st, int grid_cap) {
   constexpr int smem = 2 * 3 * (192 + 192) * 64;
   static std::atomic<unsigned long long> done{0};
-  int dev = 0;
-  hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(done.load(std::memory_order_acquire) & bit)) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3_persist192_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3_persist192_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3_persist192_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3_persist192_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    done.fetch_or(bit, std::memory_order_release);
-  }
   const long M = (long)p.B * p.OH * p.OW;
   const int mt = (int)((M + 191) / 192), nt = (p.Cout + 191) / 192;
   const long total = (long)mt * nt * (p.batch > 1 ? p.batch : 1);
   const int gm = tile_group(nt);
-  int grid = cu_count();
-  if (grid_cap > 0 && grid_cap < grid) grid = grid_cap;                  // (pf_gemm_split3_ex: leave CUs to a concurrent HBM-bound stream)
-  if (const char* s = getenv("PF_S3_GRID")) grid = atoi(s);              // (tests: fewer blocks than CUs = more tiles per block; read per call)
-  if (grid > total) grid = (int)total;
-  grid &= ~7;                                                            // (8 XCDs on gfx950: the walk gives every XCD a contiguous tile range)
-  if (total > 0x7fffffffL) return PF_ERR_ARG;
-  if (grid < 8) return PF_ERR_FALLBACK;                                  // (a PF_S3_GRID below 8 / not a number: the caller runs the one-tile kernel)
+  const int grid = pf_launch::persist_grid(pf_cu_count(), grid_cap, total, PF_GRID_CAP | PF_GRID_ENV | PF_GRID_FALLBACK);
+  if (grid < 0) return grid == PF_ERR_FALLBACK ? grid : PF_ERR_ARG;      // (fallback: the caller runs the one-tile kernel)
+  if (!pf_ensure_dynamic_lds(done, smem, gemm_split3_persist192_kernel<true, true>, gemm_split3_persist192_kernel<false, true>,
+                             gemm_split3_persist192_kernel<true, false>, gemm_split3_persist192_kernel<false, false>))
+    return PF_ERR_LAUNCH;
 #ifdef PF_S3_DBG
   const bool bare = !p.bias && !p.scale && !p.res && p.act == PF_ACT_NONE && p.out_f32;          // (res2 = the timeline buffer)
 #else
@@ -1204,28 +1168,22 @@ int launch_persist192(const pf_conv_params& p, hipStream_t st, int grid_cap) {
 // persistent 192 x 192 launch of the fp16x2 form (two planes per operand: 96 KiB of LDS); the batched BARE product only
 int launch_persist192_f16(const pf_conv_params& p, hipStream_t st, int grid_cap) {
   constexpr int stage = 2 * (192 + 192) * 64;
-  static std::atomic<unsigned long long> done{0};
-  int dev = 0;
-  hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(done.load(std::memory_order_acquire) & bit)) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3_persist192_kernel<true, true, true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * stage);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3_persist192_kernel<true, true, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * stage);
-    done.fetch_or(bit, std::memory_order_release);
-  }
+  static std::atomic<unsigned long long> done3{0}, done2{0};             // (one per ring depth: each kernel opts in to its own size)
   const char* sl = getenv("PF_F16_SLOTS");                               // (A/B: 2 = the two-slot ring of the bf16x3 kernel; read per call)
   const bool three = !(sl && sl[0] == '2');
   const long M = (long)p.B * p.OH * p.OW;
   const int mt = (int)((M + 191) / 192), nt = (p.Cout + 191) / 192;
   const long total = (long)mt * nt * (p.batch > 1 ? p.batch : 1);
   const int gm = tile_group(nt);
-  int grid = cu_count();
-  if (grid_cap > 0 && grid_cap < grid) grid = grid_cap;
-  if (grid > total) grid = (int)total;
-  grid &= ~7;
-  if (total > 0x7fffffffL || grid < 8) return PF_ERR_ARG;
-  if (three) hipLaunchKernelGGL((gemm_split3_persist192_kernel<true, true, true, 3>), dim3((unsigned)grid), dim3(512), 3 * stage, st, p, mt, nt, gm, (int)total, 8);
-  else hipLaunchKernelGGL((gemm_split3_persist192_kernel<true, true, true, 2>), dim3((unsigned)grid), dim3(512), 2 * stage, st, p, mt, nt, gm, (int)total, 8);
+  const int grid = pf_launch::persist_grid(pf_cu_count(), grid_cap, total, PF_GRID_CAP | PF_GRID_REFUSE);
+  if (grid < 0) return PF_ERR_ARG;
+  if (three) {
+    if (!pf_ensure_dynamic_lds(done3, 3 * stage, gemm_split3_persist192_kernel<true, true, true, 3>)) return PF_ERR_LAUNCH;
+    hipLaunchKernelGGL((gemm_split3_persist192_kernel<true, true, true, 3>), dim3((unsigned)grid), dim3(512), 3 * stage, st, p, mt, nt, gm, (int)total, 8);
+  } else {
+    if (!pf_ensure_dynamic_lds(done2, 2 * stage, gemm_split3_persist192_kernel<true, true, true, 2>)) return PF_ERR_LAUNCH;
+    hipLaunchKernelGGL((gemm_split3_persist192_kernel<true, true, true, 2>), dim3((unsigned)grid), dim3(512), 2 * stage, st, p, mt, nt, gm, (int)total, 8);
+  }
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
 }
 
@@ -1234,22 +1192,13 @@ int launch_persist192_f16(const pf_conv_params& p, hipStream_t st, int grid_cap)
 int launch_persist192_f16_linear(const pf_conv_params& p, hipStream_t st) {
   constexpr int smem = 3 * 2 * (192 + 192) * 64;
   static std::atomic<unsigned long long> done{0};
-  int dev = 0;
-  hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(done.load(std::memory_order_acquire) & bit)) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3_persist192_kernel<false, true, true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    done.fetch_or(bit, std::memory_order_release);
-  }
   const long M = (long)p.B * p.OH * p.OW;
   const int mt = (int)((M + 191) / 192), nt = (p.Cout + 191) / 192;
   const long total = (long)mt * nt;
   const int gm = tile_group(nt);
-  int grid = cu_count();
-  if (grid > total) grid = (int)total;
-  grid &= ~7;
-  if (grid < 8) grid = 8;
-  if (total > 0x7fffffffL) return PF_ERR_ARG;
+  const int grid = pf_launch::persist_grid(pf_cu_count(), 0, total, PF_GRID_FLOOR8);
+  if (grid < 0) return PF_ERR_ARG;
+  if (!pf_ensure_dynamic_lds(done, smem, gemm_split3_persist192_kernel<false, true, true, 3>)) return PF_ERR_LAUNCH;
   hipLaunchKernelGGL((gemm_split3_persist192_kernel<false, true, true, 3>), dim3((unsigned)grid), dim3(512), smem, st, p, mt, nt, gm, (int)total, 8);
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
 }
@@ -1258,14 +1207,8 @@ template <int BM, int BN, int WM, int WN, int NS, bool PP = false, int NP = 3, b
 int launch(const pf_conv_params& p, hipStream_t st) {
   constexpr int smem = NS * NP * (BM + BN) * 64;
   static std::atomic<unsigned long long> done{0};
-  int dev = 0;
-  hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
   auto kern = gemm_split3_kernel<BM, BN, WM, WN, NS, PP, NP, PLAIN>;
-  if (!(done.load(std::memory_order_acquire) & bit)) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    done.fetch_or(bit, std::memory_order_release);
-  }
+  if (!pf_ensure_dynamic_lds(done, smem, kern)) return PF_ERR_LAUNCH;
   const long M = (long)p.B * p.OH * p.OW;
   const long tiles = ((M + BM - 1) / BM) * ((p.Cout + BN - 1) / BN);
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)(p.batch > 1 ? p.batch : 1)), dim3(64 * WM * WN), smem, st, p);
@@ -1339,6 +1282,14 @@ int f16x2_points_route(const pf_conv_params& p, int cus, bool maxima_given = fal
 extern "C" int pf_gemm_split3_route(const pf_conv_params* p, int cus) {
   if (!p || cus <= 0) return -1;
   return split3_route(*p, cus);
+}
+
+// the grid rule of the persistent launchers (csrc/pf_launch.h) for the CPU tests: the grid, 0 = the one-tile kernel runs the call, -1 = refused
+extern "C" int pf_persist_grid(int cus, int grid_cap, long total, int policy) {
+  const int small = policy & (PF_GRID_FLOOR8 | PF_GRID_FALLBACK | PF_GRID_REFUSE);
+  if (cus <= 0 || total <= 0 || (policy & ~31) || (small != PF_GRID_FLOOR8 && small != PF_GRID_FALLBACK && small != PF_GRID_REFUSE)) return -1;
+  const int grid = pf_launch::persist_grid(cus, grid_cap, total, policy);
+  return grid == PF_ERR_FALLBACK ? 0 : grid;
 }
 
 extern "C" int pf_gemm_f16x2_points_route(const pf_conv_params* p, int cus) {
@@ -1417,7 +1368,7 @@ extern "C" int pf_gemm_split3_ex(const pf_conv_params* p, int grid_cap, void* st
 #endif
   if (e) return pf_refuse("pf_gemm_split3", e);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  switch (split3_route(*p, cu_count())) {
+  switch (split3_route(*p, pf_cu_count())) {
     case PF_S3_ROUTE_TILE64: return launch<64, 128, 2, 2, 2>(*p, st);
     case PF_S3_ROUTE_PERSIST192: {
       const int rc = launch_persist192(*p, st, grid_cap);
@@ -1438,17 +1389,7 @@ extern "C" int pf_gemm_split3_ex(const pf_conv_params* p, int grid_cap, void* st
 // fp16x2 batched product of the transform points (csrc/wino_f16x2.hip): x = V planes [2][batch][Cin/32][M][32] fp16 and w = U' planes
 // [2][batch][Cin/32][w_rows][32] fp16 (both chunk-major, korder = 6), y = float32 [batch][M][y_ld] = ldexp(sum_k w.x, col_exp[z][n]).
 extern "C" int pf_gemm_f16x2_points(const pf_conv_params* p, const int* col_exp, int grid_cap, void* stream) {
-  if (!p || !p->x || !p->w || !p->y || !col_exp) return pf_refuse("pf_gemm_f16x2_points", "null tensor");
-  if (const char* e = pf_linear_envelope(*p)) return pf_refuse("pf_gemm_f16x2_points", e);
-  if (pf_misaligned(p->x, 16) || pf_misaligned(p->w, 16) || pf_misaligned(p->y, 16) || pf_misaligned(col_exp, 16)) return pf_refuse("pf_gemm_f16x2_points", "misaligned tensor");
-  if (p->y_ld < p->Cout || p->x_bstride % 8 || p->w_bstride % 8 || (p->batch > 1 && p->y_bstride % 4)) return pf_refuse("pf_gemm_f16x2_points", "y_ld below Cout or misaligning plane strides");
-  const long M = (long)p->B * p->OH * p->OW;
-  if (p->korder != 6 || !p->out_f32) return pf_refuse("pf_gemm_f16x2_points", "korder must be 6, the output float32");
-  if (p->Cin <= 0 || p->Cin % 32 || p->x_ld != p->Cin || p->Kpad != p->Cin || p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || p->w_rows < p->Cout ||
-      p->w_rows % 4)
-    return pf_refuse("pf_gemm_f16x2_points", "argument outside the envelope (include/pf_hip.h)");
-  if (M <= 0 || M * 64 >= (1L << 31) || (long)p->w_rows * 64 >= (1L << 31) || p->x_bstride <= 0 || p->w_bstride <= 0) return pf_refuse("pf_gemm_f16x2_points", "argument outside the envelope (include/pf_hip.h)");
-  if (p->bias || p->scale || p->res || p->res2 || p->act != PF_ACT_NONE || p->batch > 65535) return pf_refuse("pf_gemm_f16x2_points", "argument outside the envelope (include/pf_hip.h)");
+  if (const int rc = f16x2_points_envelope("pf_gemm_f16x2_points", p, col_exp)) return rc;
   pf_conv_params q = *p;
   q.scale = reinterpret_cast<const float*>(col_exp);     // (int32 exponents; the kernel's F16 epilogue reads them as such)
   return launch_persist192_f16(q, reinterpret_cast<hipStream_t>(stream), grid_cap);
@@ -1475,7 +1416,7 @@ extern "C" int pf_gemm_f16x2(const pf_conv_params* p, void* stream) {
   if (!p->out_f32 && p->y_bstride <= 0) return pf_refuse("pf_gemm_f16x2", "argument outside the envelope (include/pf_hip.h)");
   if ((p->korder & 16) && (!p->out_exp || p->y_ld != p->Cout || p->Cout % 32)) return pf_refuse("pf_gemm_f16x2", "argument outside the envelope (include/pf_hip.h)");
   if ((p->korder & 32) && (!p->out_exp || p->y_ld < p->Cout || p->y_bstride % 4 || (reinterpret_cast<size_t>(p->y) & 7))) return pf_refuse("pf_gemm_f16x2", "argument outside the envelope (include/pf_hip.h)");   // 8-byte stores
-  if (f16x2_route(*p, cu_count()) == PF_S3_ROUTE_TILE160) return pf_launch_f16x2_tile160(*p, cu_count(), reinterpret_cast<hipStream_t>(stream));
+  if (f16x2_route(*p, pf_cu_count()) == PF_S3_ROUTE_TILE160) return pf_launch_f16x2_tile160(*p, pf_cu_count(), reinterpret_cast<hipStream_t>(stream));
   return launch_persist192_f16_linear(*p, reinterpret_cast<hipStream_t>(stream));
 }
 

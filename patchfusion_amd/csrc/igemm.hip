@@ -21,6 +21,7 @@
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
 #include "pf_args.h"
+#include "pf_launch.h"
 
 namespace {
 
@@ -571,18 +572,14 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_persist_kernel(const pf_con
 }
 
 
-// ---- launch helpers.  The >64 KiB dynamic-LDS opt-in is a per-DEVICE function attribute: one bit per device ordinal,
-// set atomically, so a second GPU in the same process (or a second host thread) gets its own hipFuncSetAttribute.
-// The launch status is captured ONCE (hipGetLastError clears it) and kept for pf_conv's error message. ----
+// ---- launch helpers.  The launch status is captured ONCE (hipGetLastError clears it) and kept for pf_conv's error message; a failed
+// dynamic-LDS opt-in (csrc/pf_launch.h) leaves its status there too. ----
 thread_local hipError_t g_launch_status = hipSuccess;
-inline void ensure_dynamic_lds(const void* kern, int smem, std::atomic<unsigned long long>& done) {
-  int dev = 0;
-  hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(done.load(std::memory_order_acquire) & bit)) {
-    hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    done.fetch_or(bit, std::memory_order_release);
-  }
+template <typename K>
+inline bool dynamic_lds(std::atomic<unsigned long long>& done, int smem, K kern) {
+  if (pf_ensure_dynamic_lds(done, smem, kern)) return true;
+  g_launch_status = hipGetLastError();
+  return false;
 }
 inline int launch_status() {
   g_launch_status = hipGetLastError();
@@ -610,7 +607,7 @@ int launch_persist(const pf_conv_params& p, hipStream_t st) {
   constexpr int smem = C::smem;
   static std::atomic<unsigned long long> attr_done{0};
   auto kern = gemm_persist_kernel<BM, BN, WM, WN, RELU_IN>;
-  ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, attr_done);
+  if (!dynamic_lds(attr_done, smem, kern)) return PF_ERR_LAUNCH;
   const long M = (long)p.B * p.OH * p.OW;
   const long tiles = ((M + BM - 1) / BM) * ((p.Cout + BN - 1) / BN);
   const long slots = 256L * C::occ;                      // resident blocks
@@ -837,7 +834,7 @@ int launch_big(const pf_conv_params& p, hipStream_t st) {
   constexpr int smem = 3 * (256 + 128) * 128;
   static std::atomic<unsigned long long> attr_done{0};
   auto kern = conv_igemm_big_kernel<RELU_IN>;
-  ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, attr_done);
+  if (!dynamic_lds(attr_done, smem, kern)) return PF_ERR_LAUNCH;
   const long M = (long)p.B * p.OH * p.OW;
   const long mt = (M + 255) / 256, nt = (p.Cout + 127) / 128;
   note_variant(3, 256128, p.shuffle, RELU_IN);
@@ -1254,7 +1251,7 @@ int launch_halo(const pf_conv_params& p, hipStream_t st) {
   constexpr int smem = 2 * 40960 + 2 * 3 * BN * 64;
   static std::atomic<unsigned long long> attr_done{0};
   auto kern = conv3x3_halo_kernel<WN, FM, FN, RELU_IN>;
-  ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, attr_done);
+  if (!dynamic_lds(attr_done, smem, kern)) return PF_ERR_LAUNCH;
   const long tiles = (long)p.B * ((p.H + 15) / 16) * ((p.W + 31) / 32);
   const long nt = (p.Cout + BN - 1) / BN;
   note_variant(1, WN * 100 + FM * 10 + FN, 0, RELU_IN);
@@ -1270,7 +1267,7 @@ int launch_cfg2(const pf_conv_params& p, hipStream_t st) {
   constexpr int smem = 2 * (BM + ((BN + RP - 1) / RP) * RP) * 128;
   static std::atomic<unsigned long long> attr_done{0};
   auto kern = conv_igemm_kernel<T, BM, BN, WM, WN, RELU_IN>;
-  ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, attr_done);
+  if (!dynamic_lds(attr_done, smem, kern)) return PF_ERR_LAUNCH;
   const long M = (long)p.B * p.OH * p.OW;
   const long mt = (M + BM - 1) / BM, nt = (p.Cout + BN - 1) / BN;
   note_variant(sizeof(T) == 2 ? 4 : 5, BM * 1000 + BN, p.shuffle, RELU_IN);

@@ -6,6 +6,7 @@
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
 #include "pf_args.h"
+#include "pf_launch.h"
 
 // the range pass of the fp16x2 Winograd layers (csrc/wino_f16x2.hip; not part of the C ABI)
 namespace pf_f16x2 {
@@ -1254,13 +1255,7 @@ extern "C" int pf_bins_tail(const float* clb, int clb_ld, int rel_off, const flo
     return pf_refuse("pf_bins_tail", "misaligned tensor");
   const size_t lds = (size_t)nq * BT_HID_FRAGS * 64 * 16 + 320 * 4 + 64 * 4;
   static std::atomic<unsigned long long> done{0};
-  int dev = 0;
-  hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(done.load(std::memory_order_acquire) & bit)) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(bins_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    done.fetch_or(bit, std::memory_order_release);
-  }
+  if (!pf_ensure_dynamic_lds(done, 64 * 1024, bins_tail_kernel)) return PF_ERR_LAUNCH;
   const long groups = ((long)B * H * W + 15) / 16;
   long blocks = (groups + 3) / 4;
   blocks = blocks > 512 ? 512 : blocks;                     // two resident blocks per CU, each looping over its share of the pixels

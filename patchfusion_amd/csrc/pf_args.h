@@ -36,3 +36,18 @@ inline const char* pf_linear_envelope(const pf_conv_params& p) {
   if (p.Cin <= 0 || p.Cout <= 0) return "Cin, Cout must be positive";
   return nullptr;
 }
+
+// the batched fp16x2 product of the transform points, on either tile (pf_gemm_f16x2_points, pf_gemm_f16x2_points128): PF_OK, or the refusal of `fn`
+inline int f16x2_points_envelope(const char* fn, const pf_conv_params* p, const int* col_exp) {
+  if (!p || !p->x || !p->w || !p->y || !col_exp) return pf_refuse(fn, "null tensor");
+  if (const char* e = pf_linear_envelope(*p)) return pf_refuse(fn, e);
+  if (pf_misaligned(p->x, 16) || pf_misaligned(p->w, 16) || pf_misaligned(p->y, 16) || pf_misaligned(col_exp, 16)) return pf_refuse(fn, "misaligned tensor");
+  if (p->y_ld < p->Cout || p->x_bstride % 8 || p->w_bstride % 8 || (p->batch > 1 && p->y_bstride % 4)) return pf_refuse(fn, "y_ld below Cout or misaligning plane strides");
+  const long M = (long)p->B * p->OH * p->OW;
+  if (p->korder != 6 || !p->out_f32) return pf_refuse(fn, "korder must be 6, the output float32");
+  if (p->Cin <= 0 || p->Cin % 32 || p->x_ld != p->Cin || p->Kpad != p->Cin || p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || p->w_rows < p->Cout ||
+      p->w_rows % 4 || M <= 0 || M * 64 >= (1L << 31) || (long)p->w_rows * 64 >= (1L << 31) || p->x_bstride <= 0 || p->w_bstride <= 0 || p->bias ||
+      p->scale || p->res || p->res2 || p->act != PF_ACT_NONE || p->batch > 65535)
+    return pf_refuse(fn, "argument outside the envelope (include/pf_hip.h)");
+  return PF_OK;
+}

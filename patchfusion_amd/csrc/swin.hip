@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include "../../include/pf_hip.h"
 #include "pf_args.h"
+#include "pf_launch.h"
 
 namespace {
 
@@ -336,16 +337,8 @@ int launch_wattn_mfma(const float* qkv, float* out, const float* bt, int B, int 
   constexpr int NW = 9;
   constexpr int NH = 32 / HD;
   const int lds = (3 * WTOK * 36 + NH * 529 + 2 * WTOK) * 4;
-  // (the attribute belongs to a device: one bit per device and head_dim, so that a process that drives several GPUs sets it on each)
-  static std::atomic<unsigned long long> attr_done{0};
-  int dev = 0;
-  hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(swin_window_attention_mfma_kernel<HD, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return PF_ERR_LAUNCH;
-    attr_done.fetch_or(bit, std::memory_order_release);
-  }
+  static std::atomic<unsigned long long> attr_done{0};        // (one per head_dim)
+  if (!pf_ensure_dynamic_lds(attr_done, lds, swin_window_attention_mfma_kernel<HD, NW>)) return PF_ERR_LAUNCH;
   dim3 grid(B * (Hp / WIN) * (Wp / WIN), C / 32);
   hipLaunchKernelGGL((swin_window_attention_mfma_kernel<HD, NW>), grid, dim3(NW * 64), lds, st, qkv, out, bt, Hp, Wp, C, heads, shift);
   return ok();

@@ -22,6 +22,7 @@
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
 #include "pf_args.h"
+#include "pf_launch.h"
 
 namespace {
 
@@ -349,35 +350,15 @@ int launch_output_cmax(const float* M, const pf_conv_params* p, int TH, int TW, 
 
 // the batched product of pf_gemm_f16x2_points on 128 x 128 tiles (same operands, same result bits)
 extern "C" int pf_gemm_f16x2_points128(const pf_conv_params* p, const int* col_exp, int grid_cap, void* stream) {
-  if (!p || !p->x || !p->w || !p->y || !col_exp) return pf_refuse("pf_gemm_f16x2_points128", "null tensor");
-  if (const char* e = pf_linear_envelope(*p)) return pf_refuse("pf_gemm_f16x2_points128", e);
-  if (pf_misaligned(p->x, 16) || pf_misaligned(p->w, 16) || pf_misaligned(p->y, 16) || pf_misaligned(col_exp, 16)) return pf_refuse("pf_gemm_f16x2_points128", "misaligned tensor");
-  if (p->y_ld < p->Cout || p->x_bstride % 8 || p->w_bstride % 8 || (p->batch > 1 && p->y_bstride % 4)) return pf_refuse("pf_gemm_f16x2_points128", "y_ld below Cout or misaligning plane strides");
-  const long M = (long)p->B * p->OH * p->OW;
-  if (p->korder != 6 || !p->out_f32) return pf_refuse("pf_gemm_f16x2_points128", "korder must be 6, the output float32");
-  if (p->Cin <= 0 || p->Cin % 32 || p->x_ld != p->Cin || p->Kpad != p->Cin || p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || p->w_rows < p->Cout ||
-      p->w_rows % 4)
-    return pf_refuse("pf_gemm_f16x2_points128", "argument outside the envelope (include/pf_hip.h)");
-  if (M <= 0 || M * 64 >= (1L << 31) || (long)p->w_rows * 64 >= (1L << 31) || p->x_bstride <= 0 || p->w_bstride <= 0) return pf_refuse("pf_gemm_f16x2_points128", "argument outside the envelope (include/pf_hip.h)");
-  if (p->bias || p->scale || p->res || p->res2 || p->act != PF_ACT_NONE || p->batch > 65535) return pf_refuse("pf_gemm_f16x2_points128", "argument outside the envelope (include/pf_hip.h)");
+  if (const int rc = f16x2_points_envelope("pf_gemm_f16x2_points128", p, col_exp)) return rc;
   constexpr int smem = 3 * 2 * (128 + 128) * 64;
   static std::atomic<unsigned long long> done{0};
-  int dev = 0, cus = 0;
-  hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(done.load(std::memory_order_acquire) & bit)) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16x2_persist128_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    done.fetch_or(bit, std::memory_order_release);
-  }
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  const long M = (long)p->B * p->OH * p->OW;
   const int mt = (int)((M + 127) / 128), nt = (p->Cout + 127) / 128;
   const long total = (long)mt * nt * (p->batch > 1 ? p->batch : 1);
-  int grid = cus;
-  if (grid_cap > 0 && grid_cap < grid) grid = grid_cap;
-  if (grid > total) grid = (int)total;
-  grid &= ~7;                                            // (8 XCDs on gfx950: the walk gives every XCD a contiguous tile range)
-  if (total > 0x7fffffffL) return pf_refuse("pf_gemm_f16x2_points128", "argument outside the envelope (include/pf_hip.h)");
-  if (grid < 8) grid = 8;                                // (every XCD needs a block for the walk; the blocks of an empty tile range return at once)
+  const int grid = pf_launch::persist_grid(pf_cu_count(), grid_cap, total, PF_GRID_CAP | PF_GRID_FLOOR8);
+  if (grid < 0) return pf_refuse("pf_gemm_f16x2_points128", "argument outside the envelope (include/pf_hip.h)");
+  if (!pf_ensure_dynamic_lds(done, smem, gemm_f16x2_persist128_kernel)) return PF_ERR_LAUNCH;
   pf_conv_params q = *p;
   q.scale = reinterpret_cast<const float*>(col_exp);     // (int32 exponents; the kernel's epilogue reads them as such)
   hipLaunchKernelGGL(gemm_f16x2_persist128_kernel, dim3((unsigned)grid), dim3(512), smem, reinterpret_cast<hipStream_t>(stream), q, mt, nt, (int)total);

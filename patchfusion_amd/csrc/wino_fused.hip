@@ -40,6 +40,7 @@
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
 #include "pf_args.h"
+#include "pf_launch.h"
 
 namespace {
 
@@ -519,13 +520,7 @@ __global__ __launch_bounds__(512) void wino_fused_kernel(const WF p) {
 template <int SW>
 int launch_sw(const WF& a, hipStream_t st) {
   static std::atomic<unsigned long long> attr_done{0};
-  int dev = 0;
-  hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(wino_fused_kernel<SW>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-    attr_done.fetch_or(bit, std::memory_order_release);
-  }
+  if (!pf_ensure_dynamic_lds(attr_done, LDS_TOTAL, wino_fused_kernel<SW>)) return PF_ERR_LAUNCH;
   hipLaunchKernelGGL(wino_fused_kernel<SW>, dim3((unsigned)((long)a.nsuper * a.nnb)), dim3(512), LDS_TOTAL, st, a);
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_LAUNCH;
 }

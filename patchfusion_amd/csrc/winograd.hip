@@ -15,6 +15,7 @@
 #include "pf_common.h"
 #include "../../include/pf_hip.h"
 #include "pf_args.h"
+#include "pf_launch.h"
 
 // csrc/wino_f16x2.hip
 namespace pf_f16x2 {
@@ -384,10 +385,8 @@ pf_conv_params f16x2_points_params(const pf_conv_params* p, const void* U2, int 
 int f16x2_layer_route(const pf_conv_params* p, int u_rows, bool maxima_given = false) {
   const long T = (long)p->B * ((p->H + 3) / 4) * ((p->W + 3) / 4);
   if (T > 0x7fffffffL) return -1;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
   pf_conv_params q = f16x2_points_params(p, p->x, u_rows, const_cast<void*>(p->x), static_cast<float*>(p->y), T);
-  return pf_gemm_f16x2_points_route_ex(&q, cus, maxima_given ? 1 : 0);
+  return pf_gemm_f16x2_points_route_ex(&q, pf_cu_count(), maxima_given ? 1 : 0);
 }
 
 // cmax_in != nullptr: the channel maxima of x (uint32 [Cin], of relu(x) when relu_in) are already known -- handed over by the producer's output

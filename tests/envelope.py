@@ -436,6 +436,10 @@ for _q in ("pf_gemm_split3_route", "pf_gemm_f16x2_points_route", "pf_gemm_f16x2_
     entry(_q, dict(_ROUTE_GOOD, cus=256), {}, {"null p": dict(p="NULL"), "cus=0": dict(cus=0), "cus<0": dict(cus=-8)}, no=-1, query=True)
 entry("pf_gemm_f16x2_points_route_ex", dict(_ROUTE_GOOD, cus=256, maxima_given=0), {}, {"null p": dict(p="NULL"), "cus=0": dict(cus=0), "cus<0": dict(cus=-8)}, no=-1,
       query=True)
+entry("pf_persist_grid", dict(cus=256, grid_cap=0, total=3672, policy=1 | 2 | 8), {},
+      {"cus=0": dict(cus=0), "cus<0": dict(cus=-8), "total=0": dict(total=0), "total<0": dict(total=-8), "total=2^31": dict(total=INT31),
+       "no rule below 8 blocks": dict(policy=3), "two rules below 8 blocks": dict(policy=4 | 8), "policy=32": dict(policy=32 | 8),
+       "fewer than 8 tiles, refusing": dict(total=7, policy=1 | 16)}, no=-1, query=True)
 
 # the Winograd layers: float32 3 x 3 / stride 1 / pad 1
 _W_GOOD = _pp(x_ld=32, B=1, H=4, W=4, Cin=32, y_ld=8, OH=4, OW=4, Cout=8, KH=3, KW=3, stride=1, pad=1, act=0, relu_in=0, out_f32=0, shuffle=1, dtype=0, korder=0, batch=0)

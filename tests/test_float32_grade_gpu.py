@@ -388,6 +388,52 @@ def test_fc2_static_bound_slack(lo, hi):
 
 
 # ---------------- producers ----------------
+@pytest.mark.parametrize("tile,M,N", [(128, 1024, 128), (192, 1536, 192)])
+def test_persistent_split3_below_eight_blocks_runs_the_one_tile_kernel(monkeypatch, tile, M, N):
+    """the fallback of the persistent split-GEMM launchers (csrc/pf_launch.h, PF_GRID_FALLBACK): 8 tiles route to the persistent walk under
+    PF_S3_PERSIST=2, PF_S3_GRID=4 leaves no grid of 8 blocks, and the launcher hands the call to the one 128 x 128 tile per block kernel -- the kernel
+    PF_S3_PERSIST=0 runs, so the two outputs are the same bits, and float32-grade.  (PF_S3_TILE_NOW=128 in both calls: without it 8 tiles are below
+    one round of tiles and both calls take the 64 x 128 kernel, never reaching the persistent launcher.)"""
+    import ctypes as C
+    from patchfusion_amd import _lib
+    from patchfusion_amd.hip_ops import HipOps, ops
+    K, seed = 96, 1000 + tile
+    w, b, s = _operands("random", N, K, 1, seed)
+    w = w[:, :, 0, 0]
+    x = _input((M, K), s, "random", seed + 1)
+    rows = R.sample_rows(M, n_random=192, seed=seed)
+    ref, mag = R.linear_ref(x, w, b, None, None, None, None, rows)
+    pw = pk.pack_conv_split3(w, b, scale=None, kmajor=True).to(DEV)
+    x3 = torch.stack(pk.split3(x)).to(DEV)
+    for k in ("PF_S3_PP", "PF_S3_ORDER"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("PF_S3_TILE_NOW", "128")
+    monkeypatch.setenv("PF_S3_T192", "2" if tile == 192 else "0")
+    out = {}
+    for persist, grid, route in (("2", "4", 3 if tile == 192 else 2), ("0", None, 1)):
+        monkeypatch.setenv("PF_S3_PERSIST", persist)
+        monkeypatch.setenv("PF_S3_GRID", grid) if grid else monkeypatch.delenv("PF_S3_GRID", raising=False)
+        y = torch.full((M, N), float("nan"), device=DEV)
+        assert _lib.load().pf_gemm_split3_route(C.byref(HipOps._conv_split3_plan(x3, pw, y, None, None, None)), 256) == route
+        if grid:                                                   # the launcher's grid rule answers "fall back" for this call
+            assert _lib.load().pf_persist_grid(256, 0, (M // tile) * (N // tile), 1 | 2 | 8) == 0
+        op_checks._flush_caches()
+        ops.conv_split3(x3, pw, y)
+        torch.cuda.synchronize()
+        out[persist] = y.cpu()
+    assert not torch.isnan(out["2"]).any(), "an output element was not written"
+    assert torch.equal(out["2"], out["0"])
+    e = R.errors(out["2"].double()[rows], ref, mag)
+    pw32 = pk.pack_conv(w.view(N, K, 1, 1), b, dtype=torch.float32).to(DEV)
+    y32 = torch.full((M, N), float("nan"), device=DEV)
+    op_checks._flush_caches()
+    ops.conv(x.to(DEV), pw32, y32, _direct=True)
+    torch.cuda.synchronize()
+    base = R.errors(y32.cpu()[rows], ref, mag)
+    _log(f"{f'split3_fallback_t{tile}':28s} {'rows>f32':12s} random elem {e[0]:.2e} norm {e[1]:.2e} | baseline elem {base[0]:.2e} norm {base[1]:.2e}")
+    assert R.float32_grade(e, base, R.NORM_CAP_GEMM, R.ELEM_CAP_GEMM), (e, base)
+
+
 @pytest.mark.parametrize("D", [384, 1024])
 def test_layernorm_planes_against_float64(D):
     from patchfusion_amd.hip_ops import ops
