@@ -31,6 +31,7 @@
 #include <atomic>
 #include <cstdlib>
 #include "pf_common.h"
+#include "pf_epilogue.h"
 #include "../../include/pf_hip.h"
 #include "pf_args.h"
 #include "pf_launch.h"
@@ -223,25 +224,10 @@ __global__ __launch_bounds__(4 * BM, 2) void conv1x1_split3_kernel(const pf_conv
         float v[4] = {acc[fn][fm][0] + bias_r[fn].x, acc[fn][fm][1] + bias_r[fn].y, acc[fn][fm][2] + bias_r[fn].z, acc[fn][fm][3] + bias_r[fn].w};
         acc[fn][fm] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (!nok || m >= M) continue;
-        if (p.act == PF_ACT_RELU) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-        } else if (p.act == PF_ACT_GELU) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
-        } else if (p.act == PF_ACT_SOFTPLUS) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = softplus20(v[r]);
-        }
+        epi_act(v, p.act);
         v[0] *= scale_r.x; v[1] *= scale_r.y; v[2] *= scale_r.z; v[3] *= scale_r.w;
-        if (p.res) {
-          const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.res) + (long)m * p.res_ld + n);
-          v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w;
-        }
-        if (p.res2) {
-          const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.res2) + (long)m * p.res2_ld + n);
-          v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w;
-        }
+        epi_add_res<float>(v, p.res, m, p.res_ld, n);
+        epi_add_res<float>(v, p.res2, m, p.res2_ld, n);
         *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.y) + (long)m * p.y_ld + n) = make_float4(v[0], v[1], v[2], v[3]);
       }
     }
@@ -287,15 +273,14 @@ extern "C" int pf_conv1x1_split3(const pf_conv_params* p, const void* w3, int w3
   if (const char* e = pf_linear_envelope(*p)) return pf_refuse("pf_conv1x1_split3", e);
   if (p->batch > 1) return pf_refuse("pf_conv1x1_split3", "no batch");
 #endif
-  if (p->y_ld < p->Cout || (p->res && p->res_ld < p->Cout) || (p->res2 && p->res2_ld < p->Cout)) return pf_refuse("pf_conv1x1_split3", "y_ld / residual ld below Cout");
+  // float4 loads / stores: x, y and w3 through the loaders and the store, bias and scale in registers, res and res2 in the epilogue
+  if (pf_misaligned(p->x, 16) || pf_misaligned(p->y, 16) || pf_misaligned(w3, 16)) return pf_refuse("pf_conv1x1_split3", "misaligned tensor");
+  if (const char* e = pf_epilogue_operands(*p, 16, 16)) return pf_refuse("pf_conv1x1_split3", e);
+  if (p->y_ld < p->Cout) return pf_refuse("pf_conv1x1_split3", "y_ld below Cout");
   if (p->Cin <= 0 || p->Cin % 32 || p->x_ld % 4 || p->x_ld < p->Cin) return pf_refuse("pf_conv1x1_split3", "argument outside the envelope (include/pf_hip.h)");
   if (p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || w3_rows < p->Cout || w3_rows % 16) return pf_refuse("pf_conv1x1_split3", "argument outside the envelope (include/pf_hip.h)");
-  if ((p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) return pf_refuse("pf_conv1x1_split3", "argument outside the envelope (include/pf_hip.h)");
   const long M = (long)p->B * p->OH * p->OW;
   if (M <= 0 || M >= (1L << 31) || (long)w3_rows * 64 >= (1L << 31)) return pf_refuse("pf_conv1x1_split3", "argument outside the envelope (include/pf_hip.h)");
-  // float4 loads / stores: x, y and w3 through the loaders and the store, bias and scale in registers, res and res2 in the epilogue
-  if ((reinterpret_cast<size_t>(p->x) | reinterpret_cast<size_t>(p->y) | reinterpret_cast<size_t>(w3) | reinterpret_cast<size_t>(p->res) |
-       reinterpret_cast<size_t>(p->res2) | reinterpret_cast<size_t>(p->bias) | reinterpret_cast<size_t>(p->scale)) & 15) return pf_refuse("pf_conv1x1_split3", "argument outside the envelope (include/pf_hip.h)");
   // PF_C1_BM = 64 | 128 forces a token tile (A/B, tests); default 64 (two blocks per CU).  PF_C1_PERSIST=0: one tile per block (A/B, tests).
   static const int force = [] { const char* e = getenv("PF_C1_BM"); return e ? atoi(e) : 0; }();
   static const bool persist = [] { const char* e = getenv("PF_C1_PERSIST"); return !(e && e[0] == '0'); }();

@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "pf_common.h"
+#include "pf_epilogue.h"
 #include "../../include/pf_hip.h"
 #include "pf_args.h"
 #include "pf_launch.h"
@@ -191,7 +192,6 @@ __global__ __launch_bounds__(512) void gemm_f16x2_persist160_kernel(const pf_con
         if (p.bias) bias_r = *reinterpret_cast<const float4*>(p.bias + n);
         if (p.scale) scale_r = *reinterpret_cast<const float4*>(p.scale + n);
       }
-      const int fe[4] = {fexp.x, fexp.y, fexp.z, fexp.w};
       const float bs[4] = {bias_r.x, bias_r.y, bias_r.z, bias_r.w}, sc[4] = {scale_r.x, scale_r.y, scale_r.z, scale_r.w};
 #pragma unroll
       for (int fm = 0; fm < FM; ++fm) {
@@ -199,16 +199,9 @@ __global__ __launch_bounds__(512) void gemm_f16x2_persist160_kernel(const pf_con
         acc[fn][fm] = f32x4{0.f, 0.f, 0.f, 0.f};
         acc[fn + 1][fm] = f32x4{0.f, 0.f, 0.f, 0.f};
         float v[2][4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float snd = lo ? b[r] : a[r];
-          const float recv = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, snd), 0x128, 0xf, 0xf, false));   // row_ror:8
-          v[0][r] = lo ? a[r] : recv;
-          v[1][r] = lo ? recv : b[r];
-        }
+        epi_exchange_rows(a, b, lo, v);
         const int m1 = e_m0 + wm * WTM + fm * 16 + (fr & 7);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { v[0][r] = ldexpf(v[0][r], fe[r]); v[1][r] = ldexpf(v[1][r], fe[r]); }
+        epi_ldexp_rows(v, fexp);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {                     // one row at a time (register pressure)
           __builtin_amdgcn_sched_barrier(0);
@@ -216,18 +209,10 @@ __global__ __launch_bounds__(512) void gemm_f16x2_persist160_kernel(const pf_con
           const bool ok = nok && m < M;
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[h][r] += bs[r];
-          if (p.act == PF_ACT_RELU) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[h][r] = fmaxf(v[h][r], 0.f);
-          } else if (p.act == PF_ACT_GELU) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[h][r] = gelu_erf(v[h][r]);
-          } else if (p.act == PF_ACT_SOFTPLUS) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[h][r] = softplus20(v[h][r]);
-          }
+          epi_act(v[h], p.act);
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[h][r] *= sc[r];
+          // (written out, not epi_add_res: through the helper this kernel zeroes the residual registers in another order)
           if (p.res && ok) {
             const float4 q = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.res) + (long)m * p.res_ld + n);
             v[h][0] += q.x; v[h][1] += q.y; v[h][2] += q.z; v[h][3] += q.w;

@@ -28,6 +28,7 @@
 #include <atomic>
 #include <type_traits>
 #include "pf_common.h"
+#include "pf_epilogue.h"
 #include "../../include/pf_hip.h"
 #include "pf_args.h"
 #include "pf_launch.h"
@@ -275,6 +276,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_split3_kernel(const pf_conv
       const int n = n0 + wn * WTN + fn * 16 + fg * 4;
       if (n >= p.Cout) continue;
       float v[4] = {acc[fn][fm][0] + bias_r[fn].x, acc[fn][fm][1] + bias_r[fn].y, acc[fn][fm][2] + bias_r[fn].z, acc[fn][fm][3] + bias_r[fn].w};
+      // (the chain written out, not epi_act: through the helper the two 128 x 128 instantiations order their constant moves differently)
       if (p.act == PF_ACT_RELU) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
@@ -287,27 +289,13 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_split3_kernel(const pf_conv
       }
       v[0] *= scale_r[fn].x; v[1] *= scale_r[fn].y; v[2] *= scale_r[fn].z; v[3] *= scale_r[fn].w;
       if constexpr (PLAIN) {
-        if (p.res) {
-          float a[4];
-          load4(reinterpret_cast<const bf16_t*>(p.res) + (long)m * p.res_ld + n, a);
-          v[0] += a[0]; v[1] += a[1]; v[2] += a[2]; v[3] += a[3];
-        }
-        if (p.res2) {
-          float a[4];
-          load4(reinterpret_cast<const bf16_t*>(p.res2) + (long)m * p.res2_ld + n, a);
-          v[0] += a[0]; v[1] += a[1]; v[2] += a[2]; v[3] += a[3];
-        }
+        epi_add_res<bf16_t>(v, p.res, m, p.res_ld, n);
+        epi_add_res<bf16_t>(v, p.res2, m, p.res2_ld, n);
         if (p.out_f32) *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.y) + (long)m * p.y_ld + n) = make_float4(v[0], v[1], v[2], v[3]);
         else store4(reinterpret_cast<bf16_t*>(p.y) + (long)m * p.y_ld + n, v[0], v[1], v[2], v[3]);
       } else {
-      if (p.res) {
-        const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.res) + (long)m * p.res_ld + n);
-        v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w;
-      }
-      if (p.res2) {
-        const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.res2) + (long)m * p.res2_ld + n);
-        v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w;
-      }
+      epi_add_res<float>(v, p.res, m, p.res_ld, n);
+      epi_add_res<float>(v, p.res2, m, p.res2_ld, n);
       if (p.out_f32) *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.y) + y_base + (long)m * p.y_ld + n) = make_float4(v[0], v[1], v[2], v[3]);
       else store_split3(reinterpret_cast<bf16_t*>(p.y) + split3_at(m, n, p.y_ld, (p.korder & 8) ? M : 0), p.y_bstride, v);
       }
@@ -507,25 +495,10 @@ __global__ __launch_bounds__(512) void gemm_split3_persist_kernel(const pf_conv_
             *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.y) + y_base + (long)m * p.y_ld + n) = acc[fn][fm];
           } else {
             float v[4] = {acc[fn][fm][0] + bias_r.x, acc[fn][fm][1] + bias_r.y, acc[fn][fm][2] + bias_r.z, acc[fn][fm][3] + bias_r.w};
-            if (p.act == PF_ACT_RELU) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-            } else if (p.act == PF_ACT_GELU) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
-            } else if (p.act == PF_ACT_SOFTPLUS) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) v[r] = softplus20(v[r]);
-            }
+            epi_act(v, p.act);
             v[0] *= scale_r.x; v[1] *= scale_r.y; v[2] *= scale_r.z; v[3] *= scale_r.w;
-            if (p.res) {
-              const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.res) + (long)m * p.res_ld + n);
-              v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w;
-            }
-            if (p.res2) {
-              const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.res2) + (long)m * p.res2_ld + n);
-              v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w;
-            }
+            epi_add_res<float>(v, p.res, m, p.res_ld, n);
+            epi_add_res<float>(v, p.res2, m, p.res2_ld, n);
             if (p.out_f32) *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.y) + y_base + (long)m * p.y_ld + n) = make_float4(v[0], v[1], v[2], v[3]);
             else store_split3(reinterpret_cast<bf16_t*>(p.y) + split3_at(m, n, p.y_ld, (p.korder & 8) ? M : 0), p.y_bstride, v);
           }
@@ -854,19 +827,9 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
         acc[fn][fm] = f32x4{0.f, 0.f, 0.f, 0.f};
         acc[fn + 1][fm] = f32x4{0.f, 0.f, 0.f, 0.f};
         float v[2][4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float snd = lo ? b[r] : a[r];
-          const float recv = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, snd), 0x128, 0xf, 0xf, false));   // row_ror:8
-          v[0][r] = lo ? a[r] : recv;
-          v[1][r] = lo ? recv : b[r];
-        }
+        epi_exchange_rows(a, b, lo, v);
         const int m1 = e_m0 + wm * WTM + fm * 16 + (fr & 7);
-        if constexpr (F16) {
-          const int fe[4] = {fexp.x, fexp.y, fexp.z, fexp.w};
-#pragma unroll
-          for (int r = 0; r < 4; ++r) { v[0][r] = ldexpf(v[0][r], fe[r]); v[1][r] = ldexpf(v[1][r], fe[r]); }
-        }
+        if constexpr (F16) epi_ldexp_rows(v, fexp);
         if constexpr (BARE) {
           float* yb = reinterpret_cast<float*>(p.y) + y_base;
           if (nok && m1 < M) *reinterpret_cast<float4*>(yb + (long)m1 * p.y_ld + n) = make_float4(v[0][0], v[0][1], v[0][2], v[0][3]);
@@ -882,26 +845,11 @@ __global__ __launch_bounds__(512) void gemm_split3_persist192_kernel(const pf_co
             const bool ok = nok && m < M;
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[h][r] += bs[r];
-            if (p.act == PF_ACT_RELU) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) v[h][r] = fmaxf(v[h][r], 0.f);
-            } else if (p.act == PF_ACT_GELU) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) v[h][r] = gelu_erf(v[h][r]);
-            } else if (p.act == PF_ACT_SOFTPLUS) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) v[h][r] = softplus20(v[h][r]);
-            }
+            epi_act(v[h], p.act);
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[h][r] *= sc[r];
-            if (p.res && ok) {
-              const float4 q = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.res) + (long)m * p.res_ld + n);
-              v[h][0] += q.x; v[h][1] += q.y; v[h][2] += q.z; v[h][3] += q.w;
-            }
-            if (p.res2 && ok) {
-              const float4 q = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.res2) + (long)m * p.res2_ld + n);
-              v[h][0] += q.x; v[h][1] += q.y; v[h][2] += q.z; v[h][3] += q.w;
-            }
+            epi_add_res<float>(v[h], p.res, m, p.res_ld, n, ok);
+            epi_add_res<float>(v[h], p.res2, m, p.res2_ld, n, ok);
             if (p.out_f32) {
               if (ok) *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.y) + y_base + (long)m * p.y_ld + n) = make_float4(v[h][0], v[h][1], v[h][2], v[h][3]);
             } else if (F16 && (p.korder & 16)) {
@@ -1346,15 +1294,14 @@ extern "C" int pf_gemm_split3_ex(const pf_conv_params* p, int grid_cap, void* st
 #else
   if ((e = pf_linear_envelope(*p)) != nullptr) {}
 #endif
-  else if (pf_misaligned(p->x, 16) || pf_misaligned(p->w, 16) || pf_misaligned(p->y, (p->out_f32 || (p->korder & 8)) ? 16 : 8) || pf_misaligned(p->bias, 16) ||
-           pf_misaligned(p->scale, 16) || pf_misaligned(p->res, 16) || pf_misaligned(p->res2, 16))
+  else if (pf_misaligned(p->x, 16) || pf_misaligned(p->w, 16) || pf_misaligned(p->y, (p->out_f32 || (p->korder & 8)) ? 16 : 8))
     e = "misaligned tensor (16 bytes; 8 for plane outputs)";
-  else if (p->y_ld < p->Cout || (p->res && p->res_ld < p->Cout) || (p->res2 && p->res2_ld < p->Cout)) e = "y_ld / residual ld below Cout";
+  else if ((e = pf_epilogue_operands(*p, 16, 16)) != nullptr) {}
+  else if (p->y_ld < p->Cout) e = "y_ld below Cout";
   else if (p->x_bstride % 8 || p->w_bstride % 8 || (!p->out_f32 && p->y_bstride % ((p->korder & 8) ? 8 : 4)))
     e = "plane strides must keep the planes aligned (x, w: 8 elements, y: 4, chunk-major y: 8)";
   else if (p->Cin <= 0 || p->Cin % 32 || p->Kpad < p->Cin || p->Kpad % 32 || p->x_ld % 8 || p->x_ld < p->Cin) e = "K must be a multiple of 32, x_ld of 8";
   else if (p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || p->w_rows < p->Cout) e = "Cout / y_ld must be multiples of 4";
-  else if ((p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) e = "residual ld must be a multiple of 4";
   else if ((long)p->B * p->OH * p->OW <= 0 || (long)p->B * p->OH * p->OW >= (1L << 31)) e = "bad token count";
   else if (p->x_bstride <= 0 || p->w_bstride <= 0 || (!p->out_f32 && p->y_bstride <= 0)) e = "plane strides missing";
   else if (((p->korder & 2) && p->x_ld != p->Cin) || ((p->korder & 4) && p->Kpad != p->Cin) || (p->korder & ~14)) e = "chunk-major operands are dense: x_ld == Kpad == Cin";
@@ -1399,10 +1346,11 @@ extern "C" int pf_gemm_f16x2_points(const pf_conv_params* p, const int* col_exp,
 extern "C" int pf_gemm_f16x2(const pf_conv_params* p, void* stream) {
   if (!p || !p->x || !p->w || !p->y || !p->col_exp) return pf_refuse("pf_gemm_f16x2", "null tensor");
   if (const char* e = pf_linear_envelope(*p)) return pf_refuse("pf_gemm_f16x2", e);
-  if (pf_misaligned(p->x, 16) || pf_misaligned(p->w, 16) || pf_misaligned(p->y, (p->out_f32 || (p->korder & 16)) ? 16 : 8) || pf_misaligned(p->bias, 16) ||
-      pf_misaligned(p->scale, 16) || pf_misaligned(p->res, 16) || pf_misaligned(p->res2, 16) || pf_misaligned(p->col_exp, 16) || pf_misaligned(p->out_exp, 16))
+  if (pf_misaligned(p->x, 16) || pf_misaligned(p->w, 16) || pf_misaligned(p->y, (p->out_f32 || (p->korder & 16)) ? 16 : 8) || pf_misaligned(p->col_exp, 16) ||
+      pf_misaligned(p->out_exp, 16))
     return pf_refuse("pf_gemm_f16x2", "misaligned tensor (16 bytes; 8 for plane outputs)");
-  if (p->y_ld < p->Cout || (p->res && p->res_ld < p->Cout) || (p->res2 && p->res2_ld < p->Cout)) return pf_refuse("pf_gemm_f16x2", "y_ld / residual ld below Cout");
+  if (const char* e = pf_epilogue_operands(*p, 16, 16)) return pf_refuse("pf_gemm_f16x2", e);
+  if (p->y_ld < p->Cout) return pf_refuse("pf_gemm_f16x2", "y_ld below Cout");
   if (p->x_bstride % 8 || p->w_bstride % 8 || (!p->out_f32 && p->y_bstride % ((p->korder & 16) ? 8 : 4))) return pf_refuse("pf_gemm_f16x2", "plane strides must keep the planes aligned");
   const long M = (long)p->B * p->OH * p->OW;
   if (p->batch > 1 || (p->korder & ~48) != 6 || (p->korder & 48) == 48)
@@ -1411,7 +1359,6 @@ extern "C" int pf_gemm_f16x2(const pf_conv_params* p, void* stream) {
       p->w_rows % 4)
     return pf_refuse("pf_gemm_f16x2", "argument outside the envelope (include/pf_hip.h)");
   if (M <= 0 || M * 64 >= (1L << 31) || (long)p->w_rows * 64 >= (1L << 31) || p->x_bstride <= 0 || p->w_bstride <= 0) return pf_refuse("pf_gemm_f16x2", "argument outside the envelope (include/pf_hip.h)");
-  if ((p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) return pf_refuse("pf_gemm_f16x2", "argument outside the envelope (include/pf_hip.h)");
   if (p->out_f32 && (p->korder & 48)) return pf_refuse("pf_gemm_f16x2", "argument outside the envelope (include/pf_hip.h)");
   if (!p->out_f32 && p->y_bstride <= 0) return pf_refuse("pf_gemm_f16x2", "argument outside the envelope (include/pf_hip.h)");
   if ((p->korder & 16) && (!p->out_exp || p->y_ld != p->Cout || p->Cout % 32)) return pf_refuse("pf_gemm_f16x2", "argument outside the envelope (include/pf_hip.h)");
@@ -1426,12 +1373,11 @@ extern "C" int pf_gemm_bf16_pp(const pf_conv_params* p, void* stream) {
   if (!p || !p->x || !p->w || !p->y) return pf_refuse("pf_gemm_bf16_pp", "null tensor");
   if (const char* e = pf_linear_envelope(*p)) return pf_refuse("pf_gemm_bf16_pp", e);
   if (p->dtype != PF_DTYPE_BF16 || p->batch > 1) return pf_refuse("pf_gemm_bf16_pp", "bf16, one plane only");
-  if (pf_misaligned(p->x, 16) || pf_misaligned(p->w, 16) || pf_misaligned(p->y, p->out_f32 ? 16 : 8) || pf_misaligned(p->bias, 16) || pf_misaligned(p->scale, 16) ||
-      pf_misaligned(p->res, 8) || pf_misaligned(p->res2, 8))
-    return pf_refuse("pf_gemm_bf16_pp", "misaligned tensor (16 bytes; 8 for bf16 y / res / res2)");
-  if (p->y_ld < p->Cout || (p->res && p->res_ld < p->Cout) || (p->res2 && p->res2_ld < p->Cout)) return pf_refuse("pf_gemm_bf16_pp", "y_ld / residual ld below Cout");
+  if (pf_misaligned(p->x, 16) || pf_misaligned(p->w, 16) || pf_misaligned(p->y, p->out_f32 ? 16 : 8)) return pf_refuse("pf_gemm_bf16_pp", "misaligned tensor (16 bytes; 8 for bf16 y)");
+  if (const char* e = pf_epilogue_operands(*p, 16, 8)) return pf_refuse("pf_gemm_bf16_pp", e);
+  if (p->y_ld < p->Cout) return pf_refuse("pf_gemm_bf16_pp", "y_ld below Cout");
   if (p->Cin <= 0 || p->Cin % 64 || p->Kpad < p->Cin || p->x_ld % 8 || p->x_ld < p->Cin || p->Kpad % 8) return pf_refuse("pf_gemm_bf16_pp", "argument outside the envelope (include/pf_hip.h)");
-  if (p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || p->w_rows < p->Cout || (p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) return pf_refuse("pf_gemm_bf16_pp", "argument outside the envelope (include/pf_hip.h)");
+  if (p->Cout <= 0 || p->Cout % 4 || p->y_ld % 4 || p->w_rows < p->Cout) return pf_refuse("pf_gemm_bf16_pp", "argument outside the envelope (include/pf_hip.h)");
   if ((long)p->B * p->OH * p->OW <= 0 || (long)p->B * p->OH * p->OW >= (1L << 31)) return pf_refuse("pf_gemm_bf16_pp", "argument outside the envelope (include/pf_hip.h)");
   pf_conv_params pd = *p;
   pd.korder = 0;

@@ -19,6 +19,7 @@
 //       both operands, which leaves the sum unchanged.
 #include <atomic>
 #include "pf_common.h"
+#include "pf_epilogue.h"
 #include "../../include/pf_hip.h"
 #include "pf_args.h"
 #include "pf_launch.h"
@@ -349,16 +350,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_kernel(const pf_conv_
       } else {
         v[0] += bias_r[fn].x; v[1] += bias_r[fn].y; v[2] += bias_r[fn].z; v[3] += bias_r[fn].w;
       }
-      if (p.act == PF_ACT_RELU) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-      } else if (p.act == PF_ACT_GELU) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
-      } else if (p.act == PF_ACT_SOFTPLUS) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = softplus20(v[r]);
-      }
+      epi_act(v, p.act);
       if (s > 1) {
         if (p.scale) {
 #pragma unroll
@@ -367,18 +359,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_kernel(const pf_conv_
       } else {
         v[0] *= scale_r[fn].x; v[1] *= scale_r[fn].y; v[2] *= scale_r[fn].z; v[3] *= scale_r[fn].w;
       }
-      if (p.res) {
-        float t[4];
-        load4(reinterpret_cast<const T*>(p.res) + opix * p.res_ld + co, t);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] += t[r];
-      }
-      if (p.res2) {
-        float t[4];
-        load4(reinterpret_cast<const T*>(p.res2) + opix * p.res2_ld + co, t);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] += t[r];
-      }
+      epi_add_res<T>(v, p.res, opix, p.res_ld, co);
+      epi_add_res<T>(v, p.res2, opix, p.res2_ld, co);
       if (p.out_f32) store4(reinterpret_cast<float*>(p.y) + plane * (size_t)p.y_bstride + opix * p.y_ld + co, v[0], v[1], v[2], v[3]);
       else store4(reinterpret_cast<T*>(p.y) + plane * (size_t)p.y_bstride + opix * p.y_ld + co, v[0], v[1], v[2], v[3]);
     }
@@ -541,29 +523,10 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_persist_kernel(const pf_con
         if (n >= p.Cout) continue;
         float v[4] = {acc[fn][fm][0] + bias_r[fn].x, acc[fn][fm][1] + bias_r[fn].y, acc[fn][fm][2] + bias_r[fn].z,
                       acc[fn][fm][3] + bias_r[fn].w};
-        if (p.act == PF_ACT_RELU) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-        } else if (p.act == PF_ACT_GELU) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
-        } else if (p.act == PF_ACT_SOFTPLUS) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = softplus20(v[r]);
-        }
+        epi_act(v, p.act);
         v[0] *= scale_r[fn].x; v[1] *= scale_r[fn].y; v[2] *= scale_r[fn].z; v[3] *= scale_r[fn].w;
-        if (p.res) {
-          float r4[4];
-          load4(reinterpret_cast<const T*>(p.res) + (long)m * p.res_ld + n, r4);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] += r4[r];
-        }
-        if (p.res2) {
-          float r4[4];
-          load4(reinterpret_cast<const T*>(p.res2) + (long)m * p.res2_ld + n, r4);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] += r4[r];
-        }
+        epi_add_res<T>(v, p.res, m, p.res_ld, n);
+        epi_add_res<T>(v, p.res2, m, p.res2_ld, n);
         if (p.out_f32) store4(reinterpret_cast<float*>(p.y) + (long)m * p.y_ld + n, v[0], v[1], v[2], v[3]);
         else store4(reinterpret_cast<T*>(p.y) + (long)m * p.y_ld + n, v[0], v[1], v[2], v[3]);
       }
@@ -796,32 +759,13 @@ __global__ __launch_bounds__(512) void conv_igemm_big_kernel(const pf_conv_param
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] += p.bias[co + r];
         }
-        if (p.act == PF_ACT_RELU) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-        } else if (p.act == PF_ACT_GELU) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
-        } else if (p.act == PF_ACT_SOFTPLUS) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = softplus20(v[r]);
-        }
+        epi_act(v, p.act);
         if (p.scale) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] *= p.scale[co + r];
         }
-        if (p.res) {
-          float t4[4];
-          load4(reinterpret_cast<const T*>(p.res) + opix * p.res_ld + co, t4);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] += t4[r];
-        }
-        if (p.res2) {
-          float t4[4];
-          load4(reinterpret_cast<const T*>(p.res2) + opix * p.res2_ld + co, t4);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] += t4[r];
-        }
+        epi_add_res<T>(v, p.res, opix, p.res_ld, co);
+        epi_add_res<T>(v, p.res2, opix, p.res2_ld, co);
         if (p.out_f32) store4(reinterpret_cast<float*>(p.y) + opix * p.y_ld + co, v[0], v[1], v[2], v[3]);
         else store4(reinterpret_cast<T*>(p.y) + opix * p.y_ld + co, v[0], v[1], v[2], v[3]);
       }
@@ -1212,32 +1156,13 @@ __global__ __launch_bounds__(512) void conv3x3_halo_kernel(const pf_conv_params 
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] += p.bias[co + r];
         }
-        if (p.act == PF_ACT_RELU) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-        } else if (p.act == PF_ACT_GELU) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
-        } else if (p.act == PF_ACT_SOFTPLUS) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = softplus20(v[r]);
-        }
+        epi_act(v, p.act);
         if (p.scale) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] *= p.scale[co + r];
         }
-        if (p.res) {
-          float t4[4];
-          load4(reinterpret_cast<const T*>(p.res) + opix * p.res_ld + co, t4);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] += t4[r];
-        }
-        if (p.res2) {
-          float t4[4];
-          load4(reinterpret_cast<const T*>(p.res2) + opix * p.res2_ld + co, t4);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] += t4[r];
-        }
+        epi_add_res<T>(v, p.res, opix, p.res_ld, co);
+        epi_add_res<T>(v, p.res2, opix, p.res2_ld, co);
         if (p.out_f32) store4(reinterpret_cast<float*>(p.y) + opix * p.y_ld + co, v[0], v[1], v[2], v[3]);
         else store4(reinterpret_cast<T*>(p.y) + opix * p.y_ld + co, v[0], v[1], v[2], v[3]);
       }
@@ -1478,9 +1403,8 @@ int validate(const pf_conv_params* p) {
   const unsigned ya = (p->dtype == PF_DTYPE_F32 || p->out_f32) ? 16 : 8, ra = p->dtype == PF_DTYPE_F32 ? 4 : 2;
   if (!p->x || !p->w || !p->y) e = "null tensor";
   else if (pf_bad_dtype(p->dtype)) e = "bad dtype";
-  else if (pf_misaligned(p->x, 16) || pf_misaligned(p->w, 16) || pf_misaligned(p->bias, 4) || pf_misaligned(p->scale, 4) || pf_misaligned(p->y, ya) ||
-           pf_misaligned(p->res, ra) || pf_misaligned(p->res2, ra))
-    e = "misaligned tensor (x, w: 16 bytes; y: four elements; bias, scale, res, res2: one element)";
+  else if (pf_misaligned(p->x, 16) || pf_misaligned(p->w, 16) || pf_misaligned(p->y, ya)) e = "misaligned tensor (x, w: 16 bytes; y: four elements)";
+  else if ((geo = pf_epilogue_operands(*p, 4, ra)) != nullptr) e = geo;
   else if (pf_bad_act(p->act)) e = "bad act";
   else if (p->shuffle < 1) e = "shuffle must be >= 1 (1 = none)";
   else if (p->batch < 0) e = "batch must be >= 0";
@@ -1488,8 +1412,8 @@ int validate(const pf_conv_params* p) {
   else if (p->Cin <= 0 || p->Cin % vec) e = "Cin must be a positive multiple of the 16-byte vector";
   else if (p->x_ld % vec || p->x_ld < p->Cin) e = "x_ld must be a multiple of the vector and >= Cin";
   else if (p->Cout <= 0 || p->Cout % 4) e = "Cout must be a positive multiple of 4";
-  else if (p->y_ld % 4 || (p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) e = "output/residual ld must be multiples of 4";
-  else if (p->y_ld < p->Cout / ss || (p->res && p->res_ld < p->Cout) || (p->res2 && p->res2_ld < p->Cout)) e = "output/residual ld below the channels of a pixel";
+  else if (p->y_ld % 4) e = "y_ld must be a multiple of 4";
+  else if (p->y_ld < p->Cout / ss) e = "y_ld below the channels of a pixel";
   else if (p->batch > 1 && (p->x_bstride <= 0 || p->w_bstride <= 0 || p->y_bstride <= 0)) e = "batch > 1: plane strides missing";
   else if (p->Kpad <= 0 || p->Kpad % bk) e = "Kpad must be a multiple of the 128-byte chunk";
   else if ((long)p->KH * p->KW * (p->Cin / vec) > (long)(p->Kpad / vec)) e = "Kpad smaller than KH*KW*Cin";

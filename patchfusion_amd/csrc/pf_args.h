@@ -26,6 +26,17 @@ inline const char* pf_conv_geometry(const pf_conv_params& p) {
   return nullptr;
 }
 
+// the epilogue operands of a pf_conv_params (device side: csrc/pf_epilogue.h), each optional: bias / scale off a vec_align-byte boundary, res / res2
+// off a res_align-byte one (the widest load the launcher's kernels issue through them), or a residual whose rows are not a multiple of 4 elements
+// apart or closer than Cout
+inline const char* pf_epilogue_operands(const pf_conv_params& p, unsigned vec_align, unsigned res_align) {
+  if (pf_misaligned(p.bias, vec_align) || pf_misaligned(p.scale, vec_align)) return "misaligned bias / scale";
+  if (pf_misaligned(p.res, res_align) || pf_misaligned(p.res2, res_align)) return "misaligned residual";
+  if ((p.res && (p.res_ld % 4 || p.res_ld < p.Cout)) || (p.res2 && (p.res2_ld % 4 || p.res2_ld < p.Cout)))
+    return "residual ld must be a multiple of 4 and at least Cout";
+  return nullptr;
+}
+
 // a pf_conv_params used as a LINEAR layer (the split-precision, fp16x2 and bf16 ping-pong GEMMs): M = B * OH * OW rows, 1 x 1 / stride 1 / no
 // padding / no pixel shuffle, a known activation, at most 65535 planes
 inline const char* pf_linear_envelope(const pf_conv_params& p) {

@@ -38,6 +38,7 @@
 // emitted assembly (tests/test_kernel_resources.py).  tests/wino_fused_model.py replays every index formula below lane by lane.
 #include <atomic>
 #include "pf_common.h"
+#include "pf_epilogue.h"
 #include "../../include/pf_hip.h"
 #include "pf_args.h"
 #include "pf_launch.h"
@@ -364,11 +365,8 @@ __global__ __launch_bounds__(512) void wino_fused_kernel(const WF p) {
           v[e] = o[e][qo] + be[e];
           if (p.relu) v[e] = fmaxf(v[e], 0.f);
         }
-        if (p.res) {
-          const float4 a = *reinterpret_cast<const float4*>(p.res + pix * p.res_ld + n);
-          v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w;
-        }
-        if (p.res2 && !WF_DBG(p, 128)) {
+        epi_add_res<float>(v, p.res, pix, p.res_ld, n);
+        if (p.res2 && !WF_DBG(p, 128)) {            // (its own text: the timing build's switch sits between the null check and the load)
           const float4 a = *reinterpret_cast<const float4*>(p.res2 + pix * p.res2_ld + n);
           v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w;
         }
@@ -553,10 +551,9 @@ extern "C" int pf_conv_winograd_fused_supported(const pf_conv_params* p) {
   if (!p || p->dtype != PF_DTYPE_F32 || p->KH != 3 || p->KW != 3 || p->stride != 1 || p->pad != 1 || p->shuffle != 1 || p->scale) return 0;
   if (p->B <= 0 || p->H <= 0 || p->W <= 0 || p->OH != p->H || p->OW != p->W || p->Cin % 16 || p->Cin < 32 || p->Cout % 4 || p->Cout <= 0) return 0;
   if (p->act != PF_ACT_NONE && p->act != PF_ACT_RELU) return 0;
-  if (p->x_ld % 4 || p->y_ld % 4 || (p->res && p->res_ld % 4) || (p->res2 && p->res2_ld % 4)) return 0;
-  if (p->x_ld < p->Cin || p->y_ld < p->Cout || (p->res && p->res_ld < p->Cout) || (p->res2 && p->res2_ld < p->Cout)) return 0;
+  if (p->x_ld % 4 || p->y_ld % 4 || p->x_ld < p->Cin || p->y_ld < p->Cout) return 0;
   // (float4 loads and stores; a null pointer counts as aligned here -- the launcher refuses null tensors itself)
-  if (pf_misaligned(p->x, 16) || pf_misaligned(p->y, 16) || pf_misaligned(p->bias, 16) || pf_misaligned(p->res, 16) || pf_misaligned(p->res2, 16)) return 0;
+  if (pf_misaligned(p->x, 16) || pf_misaligned(p->y, 16) || pf_epilogue_operands(*p, 16, 16)) return 0;
   const long pix = (long)p->B * p->H * p->W;
   if (pix * p->x_ld >= (1L << 31) || (long)p->B * ((p->H + 15) / 16) * ((p->W + 15) / 16) * ((p->Cout + 63) / 64) >= (1L << 31)) return 0;
   return 1;

@@ -155,6 +155,11 @@ __global__ __launch_bounds__(512) void wino_input_kernel(const float* __restrict
 
 // one thread = one tile x 4 output channels: (m+2)^2 16-byte loads from the planes of M, A^T m A, then the conv epilogue in the order of
 // pf_conv (bias -> act -> + res -> + res2) and m x m 16-byte stores (bounds-checked: H, W need not be multiples of m)
+// (The residual steps are written out, and wino_output_cmax_kernel of csrc/wino_f16x2_n256.hip repeats this body, on purpose.  Tried and not kept,
+// each for a different scalar preamble around the same arithmetic: the whole body, grid-stride loop included, in a __device__ __forceinline__ template --
+// blockDim.x is then no longer folded from __launch_bounds__(512) but loaded from the dispatch packet, and scalar allocation shifts from there; the loop
+// kept here and only the per-item body shared, or only csrc/pf_epilogue.h's epi_add_res for the residuals -- the helper's pointer parameters are generic,
+// the null tests of bias / res / res2 compare against a cast null, and the loop-invariant plane offsets are hoisted in another order.)
 template <int MT>
 __global__ __launch_bounds__(512) void wino_output_kernel(const float* __restrict__ M, int N, const float* __restrict__ bias, int relu,
                                                           const float* __restrict__ res, int res_ld, const float* __restrict__ res2,
@@ -442,15 +447,13 @@ int run_f16x2(const pf_conv_params* p, const float* U, int u_rows, void* V2, flo
 // activation other than NONE / RELU; 2^31 or more pixels.
 const char* wino_layer_refusal(const pf_conv_params* p) {
   if (!p || !p->x || !p->y) return "null tensor";
-  if (pf_misaligned(p->x, 16) || pf_misaligned(p->y, 16) || pf_misaligned(p->bias, 16) || pf_misaligned(p->res, 16) || pf_misaligned(p->res2, 16))
-    return "misaligned tensor";
+  if (pf_misaligned(p->x, 16) || pf_misaligned(p->y, 16)) return "misaligned tensor";
+  if (const char* e = pf_epilogue_operands(*p, 16, 16)) return e;
   if (p->dtype != PF_DTYPE_F32 || p->KH != 3 || p->KW != 3 || p->stride != 1 || p->pad != 1 || p->shuffle != 1 || p->scale)
     return "float32 3x3 / stride 1 / pad 1 layers without shuffle or scale only";
   if (p->B <= 0 || p->H <= 0 || p->W <= 0 || p->OH != p->H || p->OW != p->W) return "B, H, W must be positive, OH == H, OW == W";
   if (p->Cin <= 0 || p->Cout <= 0 || p->Cin % 32 || p->Cout % 8) return "Cin must be a positive multiple of 32, Cout of 8";
   if (p->x_ld % 4 || p->x_ld < p->Cin || p->y_ld % 4 || p->y_ld < p->Cout) return "x_ld, y_ld must be multiples of 4 and hold the channels";
-  if ((p->res && (p->res_ld % 4 || p->res_ld < p->Cout)) || (p->res2 && (p->res2_ld % 4 || p->res2_ld < p->Cout)))
-    return "residual ld must be a multiple of 4 and >= Cout";
   if (p->act != PF_ACT_NONE && p->act != PF_ACT_RELU) return "act must be NONE or RELU";
   if ((long)p->B * p->H * p->W >= (1L << 31)) return "too many pixels";
   return nullptr;

@@ -564,7 +564,11 @@ def gemm_split3(dt):
     if not (exact and same):
         return float("inf"), 1e-6, info[0]
     for tile, (M, K, N, act, res, res2, scale) in enumerate([(1037, 256, 544, "gelu", True, True, True), (2 * 1037, 1024, 1024, None, True, False, False),
-                                                             (777, 1024, 3072, None, False, False, False), (1037, 4096, 1024, "relu", True, False, True)]):
+                                                             (777, 1024, 3072, None, False, False, False), (1037, 4096, 1024, "relu", True, False, True),
+                                                             # the whole epilogue with softplus on a ragged last row fragment (2074 rows) and column
+                                                             # group (84 channels); K >= 96, 17 tiles of 128 rows and 11 of 192: what the persistent
+                                                             # routes need at the least (csrc/gemm_split3.hip split3_route)
+                                                             (2 * 1037, 96, 84, "softplus", True, True, True)]):
         w = torch.randn(N, K, generator=g) / K ** 0.5
         b = torch.randn(N, generator=g)
         sc = (0.5 + torch.rand(N, generator=g)) if scale else None
@@ -578,6 +582,8 @@ def gemm_split3(dt):
             ref = torch.nn.functional.gelu(ref)
         elif act == "relu":
             ref = torch.relu(ref)
+        elif act == "softplus":
+            ref = torch.nn.functional.softplus(ref)
         if sc is not None:
             ref = ref * sc.double().to(DEV)
         if r1 is not None:

@@ -213,6 +213,11 @@ def _epi(i):
             dict(res=True, xe=16), dict(act="relu", scale=True)][i % 7]
 
 
+# the whole epilogue at once -- bias, softplus, scale, res, res2 -- on the smallest shape of a kernel with a ragged last row fragment (rows not a multiple
+# of 16) and a ragged last column group (Cout a multiple of 4, not of 16): one case per kernel instantiation that shares csrc/pf_epilogue.h
+WHOLE_EPI = dict(act="softplus", scale=True, res=True, res2=True)
+
+
 # ---------------- halo kernels ----------------
 def _halo_cases():
     """every variant and channel count x RELU_IN x both maps (each overhangs the 16 x 32 tile both ways) x Cin 32 / 96 / 160 (one chunk, a whole number
@@ -230,7 +235,8 @@ def _halo_cases():
     return out
 
 
-HALO = _halo_cases()
+HALO = _halo_cases() + [(f"halo{shape}_n{cout}_c32_21x45_whole_epi", (2, 21, 45, 32, cout, 3, 1, 1), WHOLE_EPI, "random", _code(1, shape, 0, False))
+                        for shape, cout in ((121, 20), (122, 36), (242, 228), (243, 164))]
 
 
 @pytest.mark.parametrize("name,shape,opts,kind,expect", HALO, ids=[c[0] for c in HALO])
@@ -255,7 +261,7 @@ def _persist_cases():
     return out
 
 
-PERSIST_CASES = _persist_cases()
+PERSIST_CASES = _persist_cases() + [(f"persist{code}_k128_n84_whole_epi", code, 1037, 128, 84, WHOLE_EPI, "random", False) for code in PERSIST]
 
 
 def test_persist_arithmetic_restated():
@@ -296,7 +302,7 @@ def _big_cases():
     return out
 
 
-BIG = _big_cases()
+BIG = _big_cases() + [("big_1x1_c64_m1037_n100_whole_epi", _map(1037, 1) + (64, 100, 1, 1, 0), WHOLE_EPI, "random")]
 
 
 @pytest.mark.parametrize("name,shape,opts,kind", BIG, ids=[c[0] for c in BIG])
@@ -321,7 +327,8 @@ def _generic_cases():
     return out
 
 
-GEN = _generic_cases()
+GEN = _generic_cases() + [(f"gen{cfg}_1x1_c64_m270_n{cout}_whole_epi", cfg, _map(270, 1) + (64, cout, 1, 1, 0), WHOLE_EPI, "random")
+                          for cfg, cout in ((1, 148), (2, 116), (3, 84), (4, 36), (5, 20))]
 
 
 @pytest.mark.parametrize("name,cfg,shape,opts,kind", GEN, ids=[c[0] for c in GEN])
@@ -338,6 +345,7 @@ PP = [
     ("pp_m2049_k576_n516_gelu", (1, 1, 2049, 576, 516, 1, 1, 0), dict(act="gelu"), "spike"),
     ("pp_m2500_k512_n512_f32_views", (1, 50, 50, 512, 512, 1, 1, 0), dict(out_f32=True, xe=16, ye=24), "dead"),
     ("pp_m2049_k512_n516_wide", (1, 1, 2049, 512, 516, 1, 1, 0), dict(res=True), "wide"),
+    ("pp_m2049_k512_n516_whole_epi", (1, 1, 2049, 512, 516, 1, 1, 0), WHOLE_EPI, "random"),
 ]
 
 

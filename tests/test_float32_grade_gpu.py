@@ -98,6 +98,9 @@ CONV = [
     ("direct_1x1_cout16", "direct", dict(PF_CONV1X1_SPLIT3="0"), (1, 33, 47, 128, 16, 1, 1, 0), dict(act="softplus"), "wide"),
     ("direct_1x1_cout80", "direct", dict(PF_CONV1X1_SPLIT3="0"), (1, 33, 47, 168, 80, 1, 1, 0), dict(act="gelu"), "cols"),
     ("direct_1x1_dead", "direct", dict(PF_CONV1X1_SPLIT3="0"), (1, 33, 47, 128, 64, 1, 1, 0), dict(res=True), "dead"),
+    # the whole epilogue at once (bias, act, scale, res, res2) on a ragged last row fragment (1037 rows) and column group (84 = 5 x 16 + 4 channels)
+    ("direct_1x1_whole_epi", "direct", dict(PF_CONV1X1_SPLIT3="0"), (1, 17, 61, 64, 84, 1, 1, 0), dict(act="gelu", res=True, res2=True, scale=True), "random"),
+    ("s3_1x1_whole_epi", "s3_1x1", dict(PF_CONV1X1_SPLIT3="2"), (1, 17, 61, 64, 84, 1, 1, 0), dict(act="softplus", res=True, res2=True, scale=True), "random"),
     ("s3_1x1_ragged_epi", "s3_1x1", dict(PF_CONV1X1_SPLIT3="2"), (1, 17, 61, 256, 64, 1, 1, 0), dict(relu_in=True, res=True, res2=True, scale=True), "random"),
     ("s3_1x1_n80_views", "s3_1x1", dict(PF_CONV1X1_SPLIT3="2"), (2, 40, 52, 64, 80, 1, 1, 0), dict(act="gelu", xe=16, ye=8), "cols"),
     ("s3_1x1_n272_inplace", "s3_1x1", dict(PF_CONV1X1_SPLIT3="2"), (1, 37, 50, 96, 272, 1, 1, 0), dict(scale=True, res=True, inplace=True), "wide"),
@@ -385,6 +388,47 @@ def test_fc2_static_bound_slack(lo, hi):
     what, e, base = _linear_case(384, "fc2", 1037, None, "f32", "random", stress=(lo, hi))
     _log(f"{f'f16x2_fc2_slack_{lo}_{hi}':28s} {'>f32':12s} random elem {e[0]:.2e} norm {e[1]:.2e} | baseline elem {base[0]:.2e} norm {base[1]:.2e}")
     assert R.float32_grade(e, base, R.NORM_CAP_GEMM, R.ELEM_CAP_GEMM), (e, base)
+
+
+@pytest.mark.parametrize("tile", ["0", "1"], ids=["t192", "t160"])
+def test_f16x2_whole_epilogue_is_float32_grade(monkeypatch, tile):
+    """bias, softplus, scale, res and res2 at once through each fp16x2 linear tile (PF_F16_TILE forces it; the route is asserted), on the smallest
+    shape with a ragged last row fragment (1037 rows) and column group (260 = 16 x 16 + 4 channels).  The two tiles share csrc/pf_epilogue.h, so each
+    is judged against float64 here, not against the other."""
+    import ctypes as C
+    from patchfusion_amd import _lib
+    from patchfusion_amd.hip_ops import HipOps, ops
+    monkeypatch.setenv("PF_F16_TILE", tile)
+    M, K, N, seed = 1037, 64, 260, 160 + int(tile)
+    w, b, s = _operands("random", N, K, 1, seed)
+    w = w[:, :, 0, 0]
+    g = torch.Generator().manual_seed(seed + 2)
+    sc = 0.5 + torch.rand(N, generator=g)
+    x = _input((M, K), s, "random", seed + 1)
+    res, res2 = torch.randn(M, N, generator=g).to(DEV), torch.randn(M, N, generator=g).to(DEV)
+    rows = R.sample_rows(M, n_random=192, seed=seed)
+    ref, mag = R.linear_ref(x, w, b, "softplus", sc, res, res2, rows)
+    pw = pk.pack_conv_f16x2(w, b, sc, x.double().abs().amax(0)).to(DEV)
+    x2 = pk.rows_to_kmajor(torch.stack(pk.split_f16x2(torch.ldexp(x.double(), -pw.in_exp.cpu().double()[None, :]).float()))).contiguous().to(DEV)
+    y = torch.full((M, N + 4), float("nan"), device=DEV)
+    p = HipOps._conv_f16x2_plan(x2, pw, y[:, :N], "softplus", res, res2, None)
+    assert _lib.load().pf_gemm_f16x2_route(C.byref(p), 256) == (4 if tile == "1" else 3)          # PF_S3_ROUTE_TILE160 / PERSIST192
+    op_checks._flush_caches()
+    ops.conv_f16x2(x2, pw, y[:, :N], act="softplus", res=res, res2=res2)
+    torch.cuda.synchronize()
+    assert torch.isnan(y[:, N:]).all(), "columns beyond N were written"
+    assert not torch.isnan(y[:, :N]).any(), "an output element was not written"
+    e = R.errors(y[:, :N].double().cpu()[rows], ref, mag)
+    # baseline: the f32-MFMA kernel on the same float32 operands
+    pw32 = pk.pack_conv(w.reshape(N, K, 1, 1), b, dtype=torch.float32, scale=sc).to(DEV)
+    y32 = torch.full((M, N), float("nan"), device=DEV)
+    op_checks._flush_caches()
+    ops.conv(x.to(DEV), pw32, y32, act="softplus", res=res, res2=res2, _direct=True)
+    torch.cuda.synchronize()
+    base = R.errors(y32.cpu()[rows], ref, mag)
+    name = f"f16x2_whole_epi_{'t160' if tile == '1' else 't192'}"
+    _log(f"{name:28s} {'>f32':12s} random elem {e[0]:.2e} norm {e[1]:.2e} | baseline elem {base[0]:.2e} norm {base[1]:.2e}")
+    assert R.float32_grade(e, base, R.NORM_CAP_GEMM, R.ELEM_CAP_GEMM), (name, e, base)
 
 
 # ---------------- producers ----------------
