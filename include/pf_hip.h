@@ -149,6 +149,18 @@ int pf_gemm_f16x2_points(const pf_conv_params* p, const int* col_exp, int grid_c
 /* the same product on 128 x 128 tiles (csrc/wino_f16x2_n256.hip; the 256-column layers): same operands, same result bits */
 /* pf_gemm_f16x2_points128: Refused (PF_ERR_ARG): as pf_gemm_f16x2_points (fewer than 8 tiles are accepted). */
 int pf_gemm_f16x2_points128(const pf_conv_params* p, const int* col_exp, int grid_cap, void* stream);
+/* the same product on 160 x 256 tiles (csrc/wino_f16x2_t160.hip: the points mode of the tile of the ViT linears): same operands, same result bits;
+ * grid: PF_GRID_CAP | PF_GRID_FLOOR8 */
+/* pf_gemm_f16x2_points160: Refused (PF_ERR_ARG): as pf_gemm_f16x2_points (fewer than 8 tiles are accepted). */
+int pf_gemm_f16x2_points160(const pf_conv_params* p, const int* col_exp, int grid_cap, void* stream);
+/* whether the fp16x2 product of a three-step Winograd layer runs on that tile (1) or on the form pf_gemm_f16x2_points_route names (0); p = the
+ * product of the WHOLE layer (M = all its Winograd tiles), so the answer does not depend on the window; no launch.  At default switches: 1 for
+ * Cout == 256 with Cin >= 512, else 0 (profiles/r14_wino_t160_ab.md, r14_wino_t160_image_ab.md).  PF_WINO_F16_TILE (read per
+ * call): 0 = never, 1 = everywhere, 2 = the 768-column class alone (Cout == 768, Cin >= 512), 3 = the 256-column class alone (Cout == 256,
+ * Cin >= 512); 2 and 3 exist for the image-pass A/B of one class at a time.  The route queries above keep their values: this decision is separate
+ * from them. */
+/* pf_wino_f16x2_tile_route: Answers -1 for a null p or cus <= 0. */
+int pf_wino_f16x2_tile_route(const pf_conv_params* p, int cus);
 /* which of the two runs the product of a whole layer on a chip of `cus` compute units: PF_S3_ROUTE_PERSIST192, PF_S3_ROUTE_PERSIST128, or -1 when
  * the layer stays on three bf16 planes (pf_gemm_split3_route gives TILE64 / TILE128, or PF_WINO_F16X2_N256=0 for the 128-tile layers, or a 128-tile layer outside the measured rule -- K >= 512 and >= 4096 tiles; =3: every one); no launch */
 /* pf_gemm_f16x2_points_route: Answers -1 for a null p or cus <= 0. */
@@ -252,6 +264,7 @@ int pf_gemm_split3_route(const pf_conv_params* p, int cus);
  *   pf_gemm_f16x2, 192 x 192 tiles            PF_GRID_FLOOR8
  *   pf_gemm_f16x2, 160 x 256 tiles            PF_GRID_ENV | PF_GRID_FLOOR8
  *   pf_gemm_f16x2_points128                   PF_GRID_CAP | PF_GRID_FLOOR8
+ *   pf_gemm_f16x2_points160                   PF_GRID_CAP | PF_GRID_FLOOR8
  * Answers the grid; 0 where the launcher falls back to its one-tile kernel; -1 where it refuses (also total > 2^31 - 1). */
 #define PF_GRID_CAP 1
 #define PF_GRID_ENV 2

@@ -93,6 +93,7 @@ SIGNATURES = {
     "pf_wino_absmax": [vp, ci, cl, ci, ci, vp, vp],
     "pf_gemm_f16x2_points": [C.POINTER(ConvParams), vp, ci, vp],
     "pf_gemm_f16x2_points128": [C.POINTER(ConvParams), vp, ci, vp],
+    "pf_gemm_f16x2_points160": [C.POINTER(ConvParams), vp, ci, vp],
     "pf_gemm_f16x2": [C.POINTER(ConvParams), vp],
     "pf_gemm_split3": [C.POINTER(ConvParams), vp],
     "pf_gemm_split3_ex": [C.POINTER(ConvParams), ci, vp],
@@ -197,7 +198,7 @@ SIGNATURES = {
     "pf_silog_loss_bwd": [vp, vp, cl, cf, cf, cf, vp, cf, vp, vp],
 }
 NON_STATUS = ("pf_last_error", "pf_version", "pf_percentile_workspace_bytes", "pf_conv_winograd_fused_supported", "pf_gemm_split3_route",
-              "pf_gemm_f16x2_points_route", "pf_gemm_f16x2_points_route_ex", "pf_gemm_f16x2_route", "pf_conv_winograd_f16x2_supported_ex",
+              "pf_gemm_f16x2_points_route", "pf_gemm_f16x2_points_route_ex", "pf_gemm_f16x2_route", "pf_wino_f16x2_tile_route", "pf_conv_winograd_f16x2_supported_ex",
               "pf_wino_f16x2_scratch_bytes", "pf_conv_winograd_f16x2_supported", "pf_vit_attention_rpb_bf16_lds_bytes",
               "pf_conv_last_variant", "pf_pngd_par_window", "pf_persist_grid")   # entry points that do not return a status
 
@@ -234,6 +235,8 @@ def load():
     lib.pf_gemm_f16x2_points_route_ex.argtypes = [C.POINTER(ConvParams), ci, ci]
     lib.pf_gemm_f16x2_route.restype = ci                       # PF_S3_ROUTE_PERSIST192 / TILE160 (or -1): the tile form of an fp16x2 linear
     lib.pf_gemm_f16x2_route.argtypes = [C.POINTER(ConvParams), ci]
+    lib.pf_wino_f16x2_tile_route.restype = ci                  # 1 = the 160 x 256 tile, 0 = the form the points route names (or -1), not a status
+    lib.pf_wino_f16x2_tile_route.argtypes = [C.POINTER(ConvParams), ci]
     lib.pf_persist_grid.restype = ci                           # blocks of a persistent GEMM (0 = one-tile kernel, -1 = refused), not a status
     lib.pf_persist_grid.argtypes = [ci, ci, C.c_long, ci]
     lib.pf_conv_winograd_f16x2_supported_ex.restype = ci              # 1 / 0, not a status

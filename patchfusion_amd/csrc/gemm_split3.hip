@@ -1193,8 +1193,10 @@ int split3_route(const pf_conv_params& p, int cus) {
   return PF_S3_ROUTE_TILE128;
 }
 
-// Which fp16x2 kernel runs the batched transform-domain product of a three-step Winograd layer (p = the product of the WHOLE layer), or -1 when the
-// layer stays on three bf16 planes -- the whole rule in one place (pf_gemm_f16x2_points_route exposes it to the CPU tests):
+// Whether the batched transform-domain product of a three-step Winograd layer runs on two fp16 planes, and on which of the two older tiles
+// (p = the product of the WHOLE layer); -1 when the layer stays on three bf16 planes (pf_gemm_f16x2_points_route exposes the rule to the CPU tests).
+// From round 14 on this is no longer the whole rule: a layer that answers PERSIST192 or PERSIST128 here may run the same product on 160 x 256 tiles
+// instead (same bits), which pf_wino_f16x2_tile (csrc/wino_f16x2_t160.hip) decides separately; the values below are unchanged by it.
 //   PERSIST192  the bf16x3 product would walk 192 x 192 tiles: their F16 form (round 7)
 //   PERSIST128  the bf16x3 product would walk 128 x 128 tiles (the 256-column layers): gemm_f16x2_persist128_kernel, csrc/wino_f16x2_n256.hip,
 //               where the LAYER measured faster (profiles/r11_n256_sweep.md): K >= 512 and at least 4096 Winograd tiles.  The product itself gains
@@ -1260,7 +1262,9 @@ namespace {
 // of a 192 x 192 tile.  At 256 CUs and 8296 rows: N = 1024 (fc2, proj) is 264 tiles of 192 = two rounds (108) against 208 tiles of 160 x 256 =
 // one (60); N = 3072 is 704 / 624 tiles, three rounds either way, N = 4096 968 / 832, four rounds either way: 192 stays.  1037 rows: one round
 // either way.  Plane outputs (korder bits 16 / 32, three bf16 planes) exist on the 192-tile form only.  PF_F16_TILE (A/B and tests, read per call):
-// 0 = 192 everywhere, 1 = 160 x 256 wherever it is legal.
+// 0 = 192 everywhere, 1 = 160 x 256 wherever it is legal.  A batched call (batch > 1) is not a linear and always answers PERSIST192: the batched
+// Winograd product has its own 160 x 256 kernel and its own decision, pf_wino_f16x2_tile (csrc/wino_f16x2_t160.hip, PF_WINO_F16_TILE), which this
+// query does not reflect.
 int f16x2_route(const pf_conv_params& p, int cus) {
   const char* s = getenv("PF_F16_TILE");
   const char mode = s ? s[0] : 'r';

@@ -360,7 +360,8 @@ int run_split3(const pf_conv_params* p, const void* U3, int u_rows, int u_kpad, 
 // fp16x2 form (round 7, csrc/wino_f16x2.hip): per layer call the channel maxima of the input and the scaled filter planes U' (scratch:
 // [2][36][Cin/32][u_rows][32] fp16 | int32 [36][u_rows] column exponents | uint32 [Cin] channel maxima), then per window the input transform into
 // two fp16 planes, the batched product on three f16 MFMAs per term (pf_gemm_f16x2_points on 192 x 192 tiles, pf_gemm_f16x2_points128 on 128 x 128
-// for the layers whose bf16x3 product walks 128-tiles: f16x2_layer_route) and the output transform of run_split3.
+// for the layers whose bf16x3 product walks 128-tiles: f16x2_layer_route, or on 160 x 256 tiles where f16x2_layer_tile160 says so:
+// csrc/wino_f16x2_t160.hip) and the output transform of run_split3.
 // Same windows, same argument rules, one stream.
 struct F16x2Scratch { void* u2; int* fexp; unsigned* cmax; };
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -394,6 +395,22 @@ int f16x2_layer_route(const pf_conv_params* p, int u_rows, bool maxima_given = f
   return pf_gemm_f16x2_points_route_ex(&q, pf_cu_count(), maxima_given ? 1 : 0);
 }
 
+}  // namespace
+
+// the 160 x 256 tile form of the product and its per-layer decision (csrc/wino_f16x2_t160.hip)
+int pf_f16x2_points160(const pf_conv_params* p, const int* col_exp, int grid_cap, hipStream_t st);
+int pf_wino_f16x2_tile(const pf_conv_params& q, int cus);
+
+namespace {
+
+// Like the route, the tile is decided on the product of the WHOLE layer and the CU count: the same kernel, the same bits, for every window size.
+bool f16x2_layer_tile160(const pf_conv_params* p, int u_rows) {
+  const long T = (long)p->B * ((p->H + 3) / 4) * ((p->W + 3) / 4);
+  if (T > 0x7fffffffL) return false;
+  const pf_conv_params q = f16x2_points_params(p, p->x, u_rows, const_cast<void*>(p->x), static_cast<float*>(p->y), T);
+  return pf_wino_f16x2_tile(q, pf_cu_count()) == 1;
+}
+
 // cmax_in != nullptr: the channel maxima of x (uint32 [Cin], of relu(x) when relu_in) are already known -- handed over by the producer's output
 // transform -- and the memset + range pass are skipped.  cmax_out / cmax_relu: as run_split3.
 // A layer whose whole-layer route is -1 (called directly, or PF_WINO_F16X2_N256 flipped without a new plan) falls to the 192-tile product: correct
@@ -402,6 +419,7 @@ int run_f16x2(const pf_conv_params* p, const float* U, int u_rows, void* V2, flo
               const unsigned* cmax_in = nullptr, unsigned* cmax_out = nullptr, int cmax_relu = 0) {
   constexpr int MT = 4;
   const bool t128 = f16x2_layer_route(p, u_rows, cmax_in != nullptr) == PF_S3_ROUTE_PERSIST128;
+  const bool t160 = f16x2_layer_tile160(p, u_rows);
   const int TH = (p->H + MT - 1) / MT, TW = (p->W + MT - 1) / MT;
   const long Tall = (long)p->B * TH * TW;
   if (Tall > 0x7fffffffL) return PF_ERR_ARG;
@@ -426,7 +444,7 @@ int run_f16x2(const pf_conv_params* p, const float* U, int u_rows, void* V2, flo
     rc = pf_f16x2::launch_input(x, p->x_ld, p->B, p->H, p->W, p->Cin, p->relu_in, cmax, V2, TH, TW, t0, T, st);
     if (rc != PF_OK) return rc;
     const pf_conv_params q = f16x2_points_params(p, sc.u2, u_rows, V2, M, T);
-    rc = t128 ? pf_gemm_f16x2_points128(&q, sc.fexp, 0, st) : pf_gemm_f16x2_points(&q, sc.fexp, 0, st);
+    rc = t160 ? pf_f16x2_points160(&q, sc.fexp, 0, st) : t128 ? pf_gemm_f16x2_points128(&q, sc.fexp, 0, st) : pf_gemm_f16x2_points(&q, sc.fexp, 0, st);
     if (rc != PF_OK) return rc;
     if (cmax_out) {
       rc = pf_f16x2::launch_output_cmax(M, p, TH, TW, t0, T, cmax_out, cmax_relu, st);
